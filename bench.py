@@ -10,7 +10,12 @@ in HBM before the timed region.  Default workload = BASELINE.json configs[1]:
 own 256 blocks).  The north_star's 64 x 1024^2 set is measured beside it and
 reported under "headline_1024".
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the
+line (metric / value / unit / ms_per_step / dtype ...).  Everything else -- the un-hinted pass,
+parity samples against the oracle, the in-library kernel profile and rooflines, the live clock
+probe, the multi-GPU self-diagnosis, the headline_1024 / ViT-B / eigh / FD / quantized-state /
+bf16x6 legs and the CPU baseline -- runs only with --full.  --dump-outputs DIR writes what the
+timed path returned in its last step as .npy files (see dump_outputs).
 """
 import argparse
 import ctypes as C
@@ -596,6 +601,31 @@ def quant_f3(dev):
           "int8_dequantize_ms": round(md * 1e3, 3), "int8_dequantize_GBps": round(nm * 5 / md / 1e9, 1)}
 
 
+DUMP_ROOTS_BUDGET = 48 << 20   # bytes of root blocks in a --dump-outputs directory (all files < 64 MB)
+
+
+def dump_outputs(work, out_dir):
+  """--dump-outputs: what the timed path returned in its last step, for output-for-output comparison
+  of two builds on the same (seeded) inputs.
+    roots.npy              float32 [k, n, n]: root blocks; all of them when they fit in DUMP_ROOTS_BUDGET,
+                           else a fixed sample drawn with default_rng(0) (the same blocks in every run)
+    roots_block_index.npy  float64 [k]: which blocks roots.npy holds (index into the list below)
+    metrics.npy            float32 [blocks, 8]: the per-block metrics table of this rank (PS_M_*)
+  The block list is this rank's roots at N = 1 and the gathered buffer (every rank's roots, laid out
+  [part][rank][block]) at N > 1."""
+  os.makedirs(out_dir, exist_ok=True)
+  roots = work.gathered.view(-1, work.n, work.n) if work.gathered is not None else work.roots
+  total = int(roots.shape[0])
+  count = min(total, max(1, DUMP_ROOTS_BUDGET // (work.n * work.n * 4)))
+  idx = np.arange(total)
+  if count < total:
+    idx = np.sort(np.random.default_rng(0).choice(total, size=count, replace=False))
+  sample = roots[torch.from_numpy(idx).to(roots.device)]
+  np.save(os.path.join(out_dir, "roots.npy"), sample.cpu().numpy().astype(np.float32))
+  np.save(os.path.join(out_dir, "roots_block_index.npy"), idx.astype(np.float64))
+  np.save(os.path.join(out_dir, "metrics.npy"), work.metrics.cpu().numpy().astype(np.float32))
+
+
 def timed(work, steps, warmup, multi):
   import torch.distributed as dist
   t_warm = time.perf_counter()
@@ -907,10 +937,19 @@ def main():
   ap.add_argument("--no-cpu-baseline", action="store_true")
   ap.add_argument("--no-extras", action="store_true",
                   help="skip the ViT-B (cfg4) and eigh (cfg3) side measurements")
+  ap.add_argument("--full", action="store_true",
+                  help="after the timed steps, also run everything beyond the headline figure: the un-hinted pass, "
+                       "parity samples, kernel profile / rooflines / clock probe, the multi-GPU self-diagnosis, "
+                       "the side legs and the CPU baseline (--no-headline / --no-extras / --no-cpu-baseline trim it)")
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                  help="write what the timed path returned in its last step to DIR/*.npy (dump_outputs); "
+                       "bench_outputs/ is ignored by git")
   args = ap.parse_args()
 
   if args.gpus < 1:
     raise SystemExit("--gpus must be >= 1")
+  if args.steps < 1 or args.warmup < 0:
+    raise SystemExit("--steps must be >= 1 and --warmup >= 0")
   if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
     # launched plainly (`python bench.py --gpus N`): start the N ranks ourselves, one process per
     # GPU, BEFORE anything in this process touches the GPU, relay rank 0's line and exit with the
@@ -965,11 +1004,13 @@ def main():
   sec, flops = timed(work, args.steps, args.warmup, multi)
   if args.profile_hinted_only and not args.workload.startswith("eigh"):
     assert bool((work.metrics[:, 1] == 8).all()), "the preset hint is not this workload's iteration count"
+  if args.dump_outputs and rank == 0:
+    dump_outputs(work, args.dump_outputs)
   # The same step WITHOUT last recompute's iteration counts (ps_options.iters_hint): the first
   # recompute of a run, or a caller that keeps no metrics.  Every block then takes the careful
   # path (averaged M updates); reported beside the hinted number, never instead of it.
   sec_no_hint = None
-  if not args.workload.startswith("eigh") and not args.profile_hinted_only:
+  if args.full and not args.workload.startswith("eigh") and not args.profile_hinted_only:
     kept, work.hint = work.hint, None
     _refresh, work.refresh_hint = work.refresh_hint, (lambda: None)
     sec_no_hint, _ = timed(work, max(2, args.steps // 2), 1, multi)
@@ -1013,6 +1054,9 @@ def main():
               (PEAK_F32_MFMA_TFLOPS * world), 4),
       },
   }
+  if not args.full:
+    _emit(line, rank, multi)
+    return
 
   if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.workload.startswith("eigh"):
     line["parity_vs_oracle"] = parity_sample(work)
@@ -1409,6 +1453,11 @@ def main():
         cfg["vit_b_cfg4_parity_passes"] = vpar.get("passes")
   if rank == 0 and world == 1 and not args.no_cpu_baseline:
     line["cpu_baseline"] = cpu_baseline(args.workload)
+  _emit(line, rank, multi)
+
+
+def _emit(line, rank, multi):
+  """Rank 0 prints the line; every rank leaves the process group."""
   if rank == 0:
     def _plain(o):
       if isinstance(o, (np.floating, np.integer)):

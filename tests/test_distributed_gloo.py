@@ -387,7 +387,7 @@ def test_bench_multi_rank_control_flow_over_gloo(tmp_path):
   cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
          "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
          os.path.join(ROOT, "tests", "bench_selftest_launcher.py"), "--gpus", "2", "--steps", "2",
-         "--warmup", "1"]
+         "--warmup", "1", "--full"]
   r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
   assert r.returncode == 0, r.stderr[-3000:]
   lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -414,7 +414,7 @@ def test_bench_plain_launch_starts_its_own_ranks(tmp_path):
          if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
   env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
   cmd = [sys.executable, os.path.join(ROOT, "tests", "bench_selftest_launcher.py"), "--gpus", "2",
-         "--steps", "2", "--warmup", "1", "--no-extras"]
+         "--steps", "2", "--warmup", "1", "--full", "--no-extras"]
   r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
   assert r.returncode == 0, r.stderr[-3000:]
   lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -426,6 +426,70 @@ def test_bench_plain_launch_starts_its_own_ranks(tmp_path):
   cfg = line["config"]
   assert cfg["headline_1024_ms"] > 0 and cfg["headline_1024_ms_no_hint"] > 0 and cfg["ms_per_step_no_hint"] > 0
   assert all(not isinstance(v, (dict, list)) for k, v in cfg.items() if k.startswith(("headline_", "eigh_", "fd_", "vit_")))
+
+
+def _bench_plain_run(tmp_path, gpus, out_dir):
+  import json
+  import subprocess
+  env = {k: v for k, v in os.environ.items()
+         if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+  env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
+  cmd = [sys.executable, os.path.join(ROOT, "tests", "bench_selftest_launcher.py"), "--gpus", str(gpus),
+         "--steps", "3", "--warmup", "1", "--dump-outputs", str(out_dir)]
+  r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+  assert r.returncode == 0, r.stderr[-3000:]
+  lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+  assert len(lines) == 1, r.stdout[-2000:]
+  return json.loads(lines[0])
+
+
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path, gpus):
+  """A plain run (no --full) times --steps steps and prints the headline figure only; the legs of
+  --full are absent.  --dump-outputs writes the last timed step's roots and metrics as float32 /
+  float64 .npy files under 64 MB, and two runs with the same arguments dump the same arrays."""
+  a, b = tmp_path / "a", tmp_path / "b"
+  line = _bench_plain_run(tmp_path, gpus, a)
+  for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+    assert k in line, k
+  assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == gpus
+  assert line["value"] > 0 and line["ms_per_step"] > 0 and line["higher_is_better"] is True
+  for k in ("parity_vs_oracle", "roofline", "clock", "multi_gpu", "headline_1024", "vit_b_cfg4", "cpu_baseline"):
+    assert k not in line, k
+  assert line["config"]["ms_per_step_no_hint"] is None
+  _bench_plain_run(tmp_path, gpus, b)
+  names = sorted(p.name for p in a.iterdir())
+  assert names == ["metrics.npy", "roots.npy", "roots_block_index.npy"]
+  assert names == sorted(p.name for p in b.iterdir())
+  assert sum((a / n).stat().st_size for n in names) < 64 << 20
+  roots, idx, met = (np.load(a / n) for n in ("roots.npy", "roots_block_index.npy", "metrics.npy"))
+  assert roots.dtype == np.float32 and idx.dtype == np.float64 and met.dtype == np.float32
+  nb, n = 8, 16   # the launcher's shrunk cfg2 (bench_selftest_launcher.py)
+  assert roots.shape == (gpus * nb, n, n) and idx.tolist() == list(range(gpus * nb))
+  assert met.shape == (nb, 8) and np.isfinite(roots).all()
+  for n_ in names:
+    assert np.array_equal(np.load(a / n_), np.load(b / n_)), n_
+
+
+def test_bench_dump_samples_large_outputs(tmp_path):
+  """Root lists larger than the dump budget are sampled: a fixed set of blocks (the same in every run),
+  their indices beside them."""
+  import types
+  import bench
+  n, nb = 64, 40
+  roots = torch.arange(nb, dtype=torch.float32).view(nb, 1, 1).expand(nb, n, n).contiguous()
+  work = types.SimpleNamespace(gathered=None, roots=roots, n=n, metrics=torch.zeros((nb, 8)))
+  old = bench.DUMP_ROOTS_BUDGET
+  bench.DUMP_ROOTS_BUDGET = 10 * n * n * 4
+  try:
+    bench.dump_outputs(work, str(tmp_path / "a"))
+    bench.dump_outputs(work, str(tmp_path / "b"))
+  finally:
+    bench.DUMP_ROOTS_BUDGET = old
+  got, idx = np.load(tmp_path / "a" / "roots.npy"), np.load(tmp_path / "a" / "roots_block_index.npy")
+  assert got.shape == (10, n, n) and len(set(idx.tolist())) == 10 and (np.diff(idx) > 0).all()
+  assert np.array_equal(got[:, 0, 0], idx.astype(np.float32))
+  assert np.array_equal(idx, np.load(tmp_path / "b" / "roots_block_index.npy"))
 
 
 def test_bench_refuses_rank_counts_it_cannot_run(tmp_path):

@@ -4,7 +4,7 @@
 # and the every-step update(); small summaries are collected under gpurun_out/r04/.
 cd $GRAFT_REPO_ROOT
 R=gpurun_out/r04; mkdir -p $R
-timeout 1200 python3 bench.py --steps 20 --warmup 5 > $R/r04_bench_full.json 2> $R/r04_bench_full.err
+timeout 1200 python3 bench.py --full --steps 20 --warmup 5 > $R/r04_bench_full.json 2> $R/r04_bench_full.err
 bash tools/prof_cfg2.sh r04_cfg2 > $R/prof_cfg2.log 2>&1
 python3 tools/summarize_pmc2.py gpurun_out/r04_cfg2 $R/r04_cfg2_pmc_by_kernel.json > /dev/null 2>&1
 cp gpurun_out/r04_cfg2/trace/*/*kernel_stats.csv $R/r04_cfg2_kernel_stats.csv 2>/dev/null

@@ -5,10 +5,10 @@
 # small summaries are collected under gpurun_out/r05/.
 cd $GRAFT_REPO_ROOT
 R=gpurun_out/r05; mkdir -p $R
-timeout 1500 python3 bench.py --steps 20 --warmup 5 > $R/r05_bench_full.json 2> $R/r05_bench_full.err
+timeout 1500 python3 bench.py --full --steps 20 --warmup 5 > $R/r05_bench_full.json 2> $R/r05_bench_full.err
 # the N > 1 code path (RCCL init, async all-gathers, barriers, sharded ViT-B / FD legs) with a one-rank group
 PS_BENCH_FORCE_DIST=1 timeout 900 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 \
-  bench.py --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline > $R/r05_bench_rccl_world1_forced_dist.json 2> $R/r05_bench_rccl_world1.err
+  bench.py --gpus 1 --steps 5 --warmup 2 --full --no-cpu-baseline > $R/r05_bench_rccl_world1_forced_dist.json 2> $R/r05_bench_rccl_world1.err
 bash tools/prof_cfg2.sh r05_cfg2 > $R/prof_cfg2.log 2>&1
 python3 tools/summarize_pmc2.py gpurun_out/r05_cfg2 $R/r05_cfg2_pmc_by_kernel.json > /dev/null 2>&1
 cp gpurun_out/r05_cfg2/trace/*/*kernel_stats.csv $R/r05_cfg2_kernel_stats.csv 2>/dev/null

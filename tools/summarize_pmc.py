@@ -7,7 +7,7 @@ The three inputs are the *_counter_collection.csv files of
   rocprofv3 --kernel-trace --pmc FETCH_SIZE ...
   rocprofv3 --kernel-trace --pmc WRITE_SIZE ...
   rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES ...
-of `python3 bench.py --no-cpu-baseline --no-headline --no-extras --steps 2 --warmup 1`.
+of `python3 bench.py --full --no-cpu-baseline --no-headline --no-extras --steps 2 --warmup 1`.
 gfx950 correction (MI355X_MICROARCH.md, HBM section): FETCH_SIZE (KB) reports half of wide coalesced reads, so
 HBM bytes = (2 * FETCH_SIZE + WRITE_SIZE) * 1024.
 """
@@ -50,7 +50,7 @@ def main():
     summary = {
         "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE | --pmc WRITE_SIZE | --pmc GRBM_GUI_ACTIVE "
                    "SQ_VALU_MFMA_BUSY_CYCLES (three separate passes) --output-format csv -- python3 bench.py "
-                   "--no-cpu-baseline --no-headline --no-extras --steps 2 --warmup 1",
+                   "--full --no-cpu-baseline --no-headline --no-extras --steps 2 --warmup 1",
         "workload": "cfg2_256x512_p4",
         "code": code,
         "correction": "gfx950: FETCH_SIZE reports 1/2 of wide coalesced reads (MI355X_MICROARCH.md HBM section) => "

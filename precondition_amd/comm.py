@@ -17,8 +17,6 @@ from __future__ import annotations
 
 from typing import Callable, List, Optional, Sequence, Tuple
 
-import os
-
 import numpy as np
 import torch
 
@@ -371,7 +369,7 @@ def sharded_inverse_pth_roots(
   # thread and releases the GIL while it waits for the GPU.
   side_by_side = False
   if (n_phases == 2 and hip_root and compute_fn is None and not eigh and lam_of is not None and
-      dev is not None and dev.type == "cuda" and not os.environ.get("PS_SHARDED_SEQUENTIAL")):
+      dev is not None and dev.type == "cuda"):
     import torch.distributed as dist
     side_by_side = dist.get_backend(group) != "gloo"
   try:

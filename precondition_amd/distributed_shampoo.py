@@ -25,7 +25,6 @@ from __future__ import annotations
 import contextlib
 import gc
 import logging
-import os
 from typing import Any, Callable, List, Optional
 
 import numpy as np
@@ -79,8 +78,8 @@ def _collector_paused():
   collections per call; the full ones walk every object of the process (torch, numpy, the
   optimizer state) and cost ~3 ms per update() on the ViT-B tree, amortised.  The collector is
   therefore paused for the duration of the call and restored on exit: what it would have found
-  is still found, by one young-generation pass after the call.  PS_UPDATE_KEEP_GC=1 opts out."""
-  paused = gc.isenabled() and os.environ.get("PS_UPDATE_KEEP_GC", "0") != "1"
+  is still found, by one young-generation pass after the call."""
+  paused = gc.isenabled()
   if paused:
     gc.disable()
   try:
@@ -357,8 +356,7 @@ def distributed_shampoo(
     the general per-block path: FD / compression, owner-only statistics, blocks of merged
     rank > 2, the host-logic test backend."""
     if (not hasattr(backend, "transform_grads_fused") or frequent_directions or
-        compression_rank or shard_stats or
-        os.environ.get("PS_UPDATE_PLAN", "1") == "0"):
+        compression_rank or shard_stats):
       return None
     key = tuple(tuple(p.shape) for p in params_flat)
     if key not in _plan_cache:
@@ -818,8 +816,7 @@ def distributed_shampoo(
         # symmetric (mirrored tiles; W W^T).  The LOBPCG-deflated roots add a rank-k correction
         # outside those kernels and keep the reference's orientation.  A state imported from another
         # implementation may hold statistics / preconditioners that are symmetric only to rounding:
-        # P_L^T g then differs from the reference's g^T P orientation by that rounding (PS_APPLY_SYM=0
-        # under PS_DEV_ENV=1 restores the reference's orientation for such a run).
+        # P_L^T g then differs from the reference's g^T P orientation by that rounding.
         plan.apply_preconditioners(grads_flat, precs_flat, out,
                                    symmetric_precs=(not quantize_second_moment and
                                                     not lobpcg_topk_precondition))

@@ -1004,9 +1004,6 @@ def low_rank_root_batched(calls):
   return low_rank._low_rank_root_batched(calls)
 
 
-_FD_WS = {}   # (device, bytes needed) -> workspace of the last ps_fd_update_batched_f32 call (reused across steps)
-
-
 @_device_guarded
 def fd_update_batched(new_grads, prev, p, rank, decay, ridge_epsilon, error_tolerance, relative_matrix_epsilon,
                       x0, input_is_factor=False, tol=1e-5, degree=12, max_outer=14):
@@ -1036,11 +1033,9 @@ def fd_update_batched(new_grads, prev, p, rank, decay, ridge_epsilon, error_tole
   if (tuple(prev.shape) != (bsz, d, rank + 2) or tuple(x0.shape) != (bsz, d, b) or
       any(tuple(g.shape) != (d, d) for g in new_grads)):
     raise ValueError("fd_update_batched: shape mismatch")
-  key = (dev, need)
-  ws = _FD_WS.get(key)
-  if ws is None:
-    _FD_WS.clear()           # one resident workspace (2-3 GB at 8 x 4096^2): the last shape wins
-    ws = _FD_WS[key] = torch.empty((need,), dtype=torch.uint8, device=dev)
+  # 2-3 GB at 8 x 4096^2; the library joins its side stream back into the caller's before it returns, so the
+  # caching allocator's stream-ordered reuse hands the same block to the next step
+  ws = _workspace(need, dev)
   out = torch.empty((bsz, d, rank + 2), dtype=torch.float32, device=dev)
   conv = torch.empty((bsz,), dtype=torch.int32, device=dev)
   ptrs = (C.c_void_p * bsz)(*[g.data_ptr() for g in new_grads])

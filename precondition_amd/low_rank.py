@@ -19,7 +19,6 @@ reconstructed covariance, as the reference's own tests do (DST:770-885).
 """
 from __future__ import annotations
 
-import os
 from typing import List, Optional, Tuple
 
 import torch
@@ -179,7 +178,8 @@ def _gram_precision(d: int) -> str:
   BASELINE configs[4] names the bf16 MFMA for this branch) multiplies bf16 hi/lo pairs of g
   with float32 accumulation (2^-17 operand precision) and symmetrises the result; "f32" is the
   exact-f32 MFMA statistics kernel the dense optimizer always uses (the reference computes this
-  factor at HIGHEST precision, DS:1469)."""
+  factor at HIGHEST precision, DS:1469).  This and subspace._filter_precision's PS_FD_FILTER are
+  the only environment reads of the Python host: bench.py's --full fd_f32 leg sets both."""
   import os
   mode = os.environ.get("PS_FD_GRAM", "bf16x3")
   if mode not in ("f32", "bf16x3"):
@@ -278,19 +278,20 @@ def _fd_group_key(kw):
   ps = d if kw.get("padding_start") is None else int(kw["padding_start"])
   want_fd = bool(kw.get("generate_fd_metrics") and kw.get("generate_training_metrics", True))
   if (prev is None or rank <= 0 or ps != d or want_fd or d < SUBSPACE_MIN_N or
-      4 * (rank + 33) > d or os.environ.get("PS_FD_STACKED", "1") == "0"):
+      4 * (rank + 33) > d):
     return None
   return (d, rank, kw["p"], float(kw.get("decay", 1.0)), float(kw.get("ridge_epsilon", 1e-6)),
           float(kw.get("error_tolerance", 1e-6)), bool(kw.get("relative_matrix_epsilon", True)),
           bool(kw.get("new_grad_is_gram", False)), ng.device)
 
 
-def _fd_update_root_group(calls, key):
+def _fd_update_root_group(calls, key, one_call=True):
   """_fd_update_root (DS:1123-1290) for factors that share their sizes and scalars: every
   O(d r) / O(r) step runs ONCE on tensors stacked over the factors (one launch per operation
   for the whole group, two host reads per call instead of three per factor), the arithmetic of
   _fd_prepare / _fd_finish term for term.  Returns None for a factor whose block iteration did
-  not converge (the caller sends it through the general path)."""
+  not converge (the caller sends it through the general path).  one_call=False takes the
+  step-by-step path where the one library call would apply."""
   from . import subspace
   d, rank, p, decay, ridge_eps, err_tol, rel, is_gram, dev = key
   bsz, r = len(calls), rank
@@ -298,17 +299,14 @@ def _fd_update_root_group(calls, key):
   # ONE library call for the whole update (ps_fd_update_batched_f32: preparation, every outer round of the
   # subspace iteration, DS:1196-1290 and the packing) where the fused kernels apply; the start block is the
   # seeded Gaussian block of subspace.top_eigenpairs_batched, so the eigenpairs are bit-identical to the
-  # step-by-step path below (PS_FD_ONE_CALL=0 selects it; it is also the fallback for other shapes / modes).
-  if (dev.type == "cuda" and os.environ.get("PS_FD_ONE_CALL", "1") != "0" and
-      subspace._filter_precision(d) == "bf16x3" and subspace._fused_filter() and
-      all(os.environ.get(k_, "1") != "0" for k_ in ("PS_FD_TILED", "PS_FD_ROUND_CALL", "PS_FD_FRAG", "PS_FD_RR_X6",
-                                                     "PS_FD_PLANS", "PS_FD_ROUND_LIB", "PS_FD_CHOLQR"))):
+  # step-by-step path below (one_call=False selects it; it is also the fallback for other shapes / modes).
+  if one_call and dev.type == "cuda" and subspace._filter_precision(d) == "bf16x3":
     b = int(kernels.lib().ps_fd_block_columns(r, d))
     gen = torch.Generator(device=dev).manual_seed(1729)
     x0 = torch.randn((bsz, d, b), generator=gen, device=dev, dtype=torch.float32)
     res = kernels.fd_update_batched(
         [kw["new_grad"].contiguous() for kw in calls], prev.contiguous(), p, r, decay, ridge_eps, err_tol, rel, x0,
-        input_is_factor=not is_gram, degree=int(os.environ.get("PS_FD_DEGREE", 12)))
+        input_is_factor=not is_gram, degree=12)
     if res is not None:
       packed, conv, _ = res
       ok = conv.cpu().tolist()
@@ -367,11 +365,12 @@ def _fd_update_root_group(calls, key):
   return [(packed[j], _metrics(0.0)) if ok[j] else None for j in range(bsz)]
 
 
-def _fd_update_root_batched(calls) -> list:
+def _fd_update_root_batched(calls, *, one_call=True) -> list:
   """_fd_update_root for a list of keyword dicts.  The eigen-step of all of them runs
   batched: covariance updates of size >= SUBSPACE_MIN_N take their leading rank+1
   eigenpairs from subspace.top_eigenpairs_batched (MFMA GEMMs), the others (and any
-  that does not converge) the full blocked-Jacobi eigendecomposition."""
+  that does not converge) the full blocked-Jacobi eigendecomposition.  one_call: see
+  _fd_update_root_group."""
   n_calls = len(calls)
   results = [None] * n_calls
   preps = [None] * n_calls
@@ -382,7 +381,7 @@ def _fd_update_root_batched(calls) -> list:
     if key is not None:
       by_key.setdefault(key, []).append(i)
   for key, idxs in by_key.items():
-    for i, res in zip(idxs, _fd_update_root_group([calls[i] for i in idxs], key)):
+    for i, res in zip(idxs, _fd_update_root_group([calls[i] for i in idxs], key, one_call)):
       results[i] = res
   for i, kw in enumerate(calls):
     if results[i] is not None:

@@ -16,7 +16,6 @@ optimizer keeps its general per-block path.
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -229,8 +228,7 @@ class TreePlan:
     ta["a"] = gp[self.a_param] + self.a_goff
     ta["b"] = pp[self.a_stat]
     ta["c"] = np.where(self.a_c_is_res, rp[self.a_param], xp) + self.a_coff
-    sym = (symmetric_precs and len(getattr(self, "sa_tbl", ())) > 0 and
-           os.environ.get("PS_APPLY_SYM", "1") != "0")
+    sym = symmetric_precs and len(getattr(self, "sa_tbl", ())) > 0
     if sym:
       vec = ta[self.a_vec_rows]
       sa = self.sa_tbl.copy()
@@ -318,8 +316,7 @@ class DonatedStep:
     ta = pl.a_tbl.copy()
     ta["b"] = prp[pl.a_stat] if len(ta) else prp[:0]
     ta["c"] = (np.where(pl.a_c_is_res, rp[pl.a_param], xp) + pl.a_coff) if len(ta) else prp[:0]
-    self.sym = bool(symmetric_precs and len(getattr(pl, "sa_tbl", ())) > 0 and
-                    os.environ.get("PS_APPLY_SYM", "1") != "0")
+    self.sym = bool(symmetric_precs and len(getattr(pl, "sa_tbl", ())) > 0)
     if self.sym:
       vec = ta[pl.a_vec_rows]
       sa = pl.sa_tbl.copy()

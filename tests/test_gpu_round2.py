@@ -486,12 +486,14 @@ def test_update_tree_plan_bit_identical_to_per_block_path(device, monkeypatch):
   state are bit-identical over several steps incl. a preconditioner recompute, on a tree with
   vector, matrix, blocked (ragged) and skipped parameters."""
   import precondition_amd as pa
+  from precondition_amd.plan import TreePlan
   rng = np.random.default_rng(31)
   shapes = [(96,), (64, 48), (200, 72), (3, 4, 40), (130,), ()]
   params = [torch.tensor(rng.standard_normal(s).astype(np.float32), device=device) for s in shapes]
 
   def run(plan):
-    monkeypatch.setenv("PS_UPDATE_PLAN", "1" if plan else "0")
+    if not plan:   # no tree plan: the optimizer takes the per-block path
+      monkeypatch.setattr(TreePlan, "build", staticmethod(lambda *args: None))
     opt = pa.distributed_shampoo(0.1, 64, preconditioning_compute_steps=2,
                                  start_preconditioning_step=2,
                                  graft_type=pa.GraftingType.RMSPROP_NORMALIZED,

@@ -169,10 +169,10 @@ def test_expired_power_iteration_restart_with_stream_groups(device, monkeypatch)
 
 
 @pytest.mark.parametrize("d,rank,bsz,factor", [(1024, 8, 3, False), (2048, 64, 2, False), (1024, 20, 2, True)])
-def test_fd_update_one_library_call_equals_the_step_by_step_path(d, rank, bsz, factor, device, monkeypatch):
+def test_fd_update_one_library_call_equals_the_step_by_step_path(d, rank, bsz, factor, device):
   """ps_fd_update_batched_f32 (SURVEY 8(b)'s ps_fd_update_batched; DS:1123-1290 for a group of factors in ONE
   call: preparation, every outer round of the subspace iteration, deflation / masks / packing) against the
-  step-by-step Python-driven path (PS_FD_ONE_CALL=0: the same library calls issued one by one + torch
+  step-by-step Python-driven path (one_call=False: the same library calls issued one by one + torch
   elementwise ops): two chained updates, the packed sketches agree to float32 rounding (the eigenpairs come from
   the same calls on the same start block; only the column norms of the finish are summed in another order), and
   both match the oracle's SVD-based update (float32 sgesdd) through what the optimizer uses."""
@@ -189,7 +189,6 @@ def test_fd_update_one_library_call_equals_the_step_by_step_path(d, rank, bsz, f
       gs.append(g)
     grads.append(gs)
   for one_call in ("1", "0"):
-    monkeypatch.setenv("PS_FD_ONE_CALL", one_call)
     prevs = [torch.zeros((d, rank + 2), dtype=torch.float32, device=device) for _ in range(bsz)]
     chain = []
     for t in range(2):
@@ -204,11 +203,10 @@ def test_fd_update_one_library_call_equals_the_step_by_step_path(d, rank, bsz, f
           new_grad = gram
         calls.append(dict(new_grad=new_grad, p=4, rank=rank, ridge_epsilon=1e-6, decay=0.999, padding_start=d,
                           prev=prevs[j], new_grad_is_gram=not factor))
-      res = low_rank._fd_update_root_batched(calls)
+      res = low_rank._fd_update_root_batched(calls, one_call=one_call == "1")
       prevs = [r[0] for r in res]
       chain.append([p_.cpu().numpy() for p_ in prevs])
     outs[one_call] = chain
-  monkeypatch.delenv("PS_FD_ONE_CALL")
   for t in range(2):
     for a, b in zip(outs["1"][t], outs["0"][t]):
       assert a.shape == b.shape == (d, rank + 2)

@@ -110,3 +110,16 @@ def test_environment_is_read_in_one_function_only():
   assert src.count("void ps_dev_env_overrides(") == 1 and 'getenv("PS_DEV_ENV")' in src
   body = src[src.index("void ps_dev_env_overrides("):src.index("}  // namespace\n")]
   assert src.count("getenv(") == body.count("getenv(")
+
+
+def test_python_host_reads_two_environment_switches_only():
+  """The Python twin of the test above: no module of the package reads the environment, except
+  PS_FD_FILTER (subspace.py) and PS_FD_GRAM (low_rank.py), which bench.py's fd_f32 leg sets."""
+  pkg = os.path.join(ROOT, "precondition_amd")
+  allowed = {"subspace.py": 'os.environ.get("PS_FD_FILTER", "bf16x3")',
+             "low_rank.py": 'os.environ.get("PS_FD_GRAM", "bf16x3")'}
+  for name in sorted(os.listdir(pkg)):
+    if name.endswith(".py"):
+      reads = [ln.strip() for ln in open(os.path.join(pkg, name)) if re.search(r"\benviron\b|getenv", ln)]
+      want = [f"mode = {allowed[name]}"] if name in allowed else []
+      assert reads == want, (name, reads)

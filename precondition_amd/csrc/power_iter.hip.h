@@ -21,6 +21,12 @@
 // compares a_ij with a_ji bit for bit (one pass over the matrices, before the first step)
 // and sets a per-block flag; blocks that are not exactly symmetric read BOTH tiles (I,J)
 // and (J,I) in their off-diagonal workgroups and form the full mat-vec.
+//
+// Three executions, bit-identical by construction (the same per-tile arithmetic and the same
+// fixed-order reductions): the streaming kernels above; pi_block_kernel, ONE workgroup per block
+// of up to 4 x 4 tiles (n <= 512) with the whole block resident in its CU (registers + packed
+// diagonal tiles in LDS); and pi_resident_kernel, register-resident teams of workgroups for the
+// larger blocks.  PiPlan::enqueue routes each block.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -704,6 +710,353 @@ static __global__ __launch_bounds__(256, NT >= 3 ? 2 : (NT == 2 ? 3 : 4)) void p
   }
 }
 
+// ==================================================================================
+// Resident execution of a small block: ONE workgroup holds the whole block (t <= 4).
+// ==================================================================================
+// A block of up to 512 x 512 has at most 6 off-diagonal and 4 diagonal upper tiles.  512
+// threads = two groups of 4 wavefronts (2 waves per SIMD, 256 registers per lane): group g
+// keeps the off-diagonal tiles g, g + 2, g + 4 (row-major order of (I < J)) in registers
+// (192 VGPRs); the diagonal tiles live in LDS as packed upper triangles (4 x 33 KiB).  A step is
+// pi_mv_kernel's tile arithmetic (each group runs the 256-thread layout of one tile at a time)
+// into a [t][t][128] slab in LDS, then pi_red_kernel's 512-thread reduction: nothing leaves the
+// CU between steps and nothing waits on another workgroup, so the launch needs no co-residency
+// and a batch larger than the chip runs in dispatch waves.
+//
+// Packed diagonal tile: row i keeps columns 4 (i >> 2) .. 127 (whole float4 chunks; the 4 x 4
+// diagonal block is stored in full), chunk k of the row at rb[i] + 4 k with its 4 elements rotated
+// by (i >> 2) & 3.  Row r of the tile is rebuilt lane by lane: a chunk C >= r >> 2 is one 16-byte
+// read of row r; a chunk C < r >> 2 is column r of rows 4C .. 4C+3 (a_rc == a_cr: valid for exactly
+// symmetric blocks only -- the others read their diagonal tiles from memory in every step).  The
+// bank of such a column read (row 4C + e) is 4 ((rb / 4 - C + r / 4) mod 8) + ((r + C) & 3); the
+// row starts rb[] are padded so that (rb / 4 - C) mod 8 differs between the rows of one (e, C & 3)
+// class, which makes the 32 lanes of a column read hit 32 distinct banks.
+constexpr int PI_BLOCK_T = 4;                          // largest t of the one-workgroup kernel
+struct PiDiagLayout {
+  int rb[PT];   // row starts (floats, multiples of 4)
+  int total;    // floats per packed tile
+};
+constexpr PiDiagLayout pi_diag_layout(int maxuse) {
+  PiDiagLayout L{};
+  int used[4][4][8] = {};
+  int cur = 0;
+  for (int i = 0; i < PT; ++i) {
+    const int C = i >> 2, e = i & 3;
+    int base = cur;
+    while (used[e][C & 3][((base >> 2) - C) & 7] >= maxuse) base += 4;
+    ++used[e][C & 3][((base >> 2) - C) & 7];
+    L.rb[i] = base;
+    cur = base + PT - 4 * C;
+  }
+  L.total = cur;
+  return L;
+}
+// LDS besides the diagonal tiles (floats): slab [4][4][128], iterate [512], column partials
+// [2 groups][2 buffers][4 waves][128] (the step's y aliases them), rb[128], reduction [16]
+constexpr int PI_BLOCK_MISC = 16 * PT + 4 * PT + 16 * PT + PT + 16;
+constexpr int PI_BLOCK_LDS_MAX = 160 * 1024 / 4;
+constexpr PiDiagLayout pi_diag_fit() {
+  for (int m = 1; m < 16; ++m) {   // conflict-free column reads (m = 1) if they fit
+    const PiDiagLayout L = pi_diag_layout(m);
+    if (4 * L.total + PI_BLOCK_MISC <= PI_BLOCK_LDS_MAX) return L;
+  }
+  return pi_diag_layout(16);
+}
+constexpr PiDiagLayout kPiDiag = pi_diag_fit();
+static_assert(4 * kPiDiag.total + PI_BLOCK_MISC <= PI_BLOCK_LDS_MAX, "packed diagonal tiles exceed LDS");
+constexpr size_t PI_BLOCK_LDS = sizeof(float) * (size_t)(4 * kPiDiag.total + PI_BLOCK_MISC);
+static __constant__ PiDiagLayout pi_diag_tab = kPiDiag;
+
+// q-th off-diagonal tile (I < J, row-major order) of a block with t tiles per side.
+__device__ __forceinline__ void pi_offdiag_tile(int t, int q, int& I, int& J) {
+  I = 0;
+  while (q >= t - 1 - I) { q -= t - 1 - I; ++I; }
+  J = I + 1 + q;
+}
+
+// One off-diagonal tile from registers, 256 threads: pi_mv_kernel's arithmetic, term for term.
+// Row sums go to the slab; the per-wave column sums go to wq[4][128] (summed by the caller after
+// a barrier, in pi_mv_kernel's order); non-symmetric blocks stream the mirrored tile instead.
+__device__ __forceinline__ void pi_blk_offdiag(const PiBlock* pb, const f32x4 (&x)[16], int I, int J,
+                                               int t, const float* vn, float* P, float* wq, bool asym,
+                                               int wave, int c4, int rh) {
+  asm volatile("" : "+v"(c4), "+v"(rh), "+v"(wave));   // see pi_blk_diag
+  const int r0 = I * PT, c0 = J * PT;
+  const float* vI = vn + r0;
+  const f32x4 vj = *reinterpret_cast<const f32x4*>(vn + c0 + 4 * c4);
+  float* Pu = P + (I * t + J) * PT;
+  f32x4 w = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int it = 0; it < 16; ++it) {
+    const int r = 32 * wave + 2 * it + rh;
+    const float u = pi_half_sum(pi_dot4(x[it], vj));
+    if (c4 == PI_SUM_LANE) Pu[r] = u;
+    const float vi = vI[r];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) w[e] = __fmaf_rn(x[it][e], vi, w[e]);
+  }
+  if (asym) {
+    // pi_tile_from_regs's rare path: the mirrored tile (J, I) from memory, a few rows at a time
+    const f32x4 vi4 = *reinterpret_cast<const f32x4*>(vI + 4 * c4);
+    const int n = pb->n, lda = pb->lda;
+    const bool fast = pb->vec_ok && c0 + PT <= n && r0 + PT <= n;
+    const float* a = pb->a;
+    float* Pw = P + (J * t + I) * PT;
+#pragma unroll 2
+    for (int it = 0; it < 16; ++it) {
+      const int r = 32 * wave + 2 * it + rh;
+      f32x4 xx = {0.f, 0.f, 0.f, 0.f};
+      if (fast) {
+        xx = gload4(a + (int64_t)(c0 + r) * lda + r0 + 4 * c4);
+      } else if (c0 + r < n) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (r0 + 4 * c4 + e < n) xx[e] = gload1(a + (int64_t)(c0 + r) * lda + r0 + 4 * c4 + e);
+      }
+      const float u = pi_half_sum(pi_dot4(xx, vi4));
+      if (c4 == PI_SUM_LANE) Pw[r] = u;
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) w[e] += __shfl_xor(w[e], 32, 64);
+    if (rh == 0) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) wq[wave * PT + 4 * c4 + e] = w[e];
+    }
+  }
+}
+
+// One diagonal tile, 256 threads: pi_mv_kernel's row sums, the tile rebuilt from its packed upper
+// triangle Dx (symmetric blocks) or read from memory (the others).
+__device__ __forceinline__ void pi_blk_diag(const PiBlock* pb, const float* Dx, int X, int t,
+                                            const float* vn, float* P, const int* rbs, bool asym,
+                                            int wave, int c4, int rh) {
+  const int o = X * PT;
+  const f32x4 vj = *reinterpret_cast<const f32x4*>(vn + o + 4 * c4);
+  float* Pu = P + (X * t + X) * PT;
+  if (asym) {
+    const int n = pb->n, lda = pb->lda;
+    const bool fast = pb->vec_ok && o + PT <= n;
+    const float* a = pb->a;
+#pragma unroll 2
+    for (int it = 0; it < 16; ++it) {
+      const int r = 32 * wave + 2 * it + rh;
+      f32x4 xx = {0.f, 0.f, 0.f, 0.f};
+      if (fast) {
+        xx = gload4(a + (int64_t)(o + r) * lda + o + 4 * c4);
+      } else if (o + r < n) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (o + 4 * c4 + e < n) xx[e] = gload1(a + (int64_t)(o + r) * lda + o + 4 * c4 + e);
+      }
+      const float u = pi_half_sum(pi_dot4(xx, vj));
+      if (c4 == PI_SUM_LANE) Pu[r] = u;
+    }
+    return;
+  }
+  // Per-lane bases, re-derived in every call from opaque copies of the lane coordinates: hoisted
+  // out of the step loop they would sit beside the 192 registers of matrix data (and spill).
+  int c4v = c4, rhv = rh, wv = wave;
+  asm volatile("" : "+v"(c4v), "+v"(rhv), "+v"(wv));
+  // row r = 32 wave + 2 it + rh, R = r >> 2 = 8 wave + (it >> 1)
+  const int d = c4v - 8 * wv;                 // c4 >= R  <=>  d >= it >> 1
+  const float* up = Dx + 4 * d;               // row chunk c4 of row r: up + rb[r] - 4 (it >> 1)
+  const int* rrow = rbs + 32 * wv + rhv;      // rb[r] = rrow[2 it]
+  // column chunk of rows 4 c4 + e: Dx + rb[4 c4 + e] + 4 (R - c4) + ((r + c4) & 3)
+  const int m0 = (rhv + c4v) & 3, m1 = (m0 + 2) & 3;   // (r + c4) & 3 for even / odd it
+  const float* lo[2][4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int b = rbs[4 * c4v + e] - 4 * c4v + 32 * wv;
+    lo[0][e] = Dx + b + m0;
+    lo[1][e] = Dx + b + m1;
+  }
+#pragma unroll
+  for (int it = 0; it < 16; ++it) {
+    const int h = it >> 1, rot = h & 3;   // rot == R & 3
+    f32x4 xx;
+    if (d >= h) {
+      const f32x4 q = *reinterpret_cast<const f32x4*>(up + rrow[2 * it] - 4 * h);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) xx[e] = q[(e + rot) & 3];
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) xx[e] = lo[it & 1][e][4 * h];
+    }
+    const float u = pi_half_sum(pi_dot4(xx, vj));
+    if (c4 == PI_SUM_LANE) Pu[32 * wave + 2 * it + rh] = u;
+  }
+}
+
+static __global__ __launch_bounds__(512, 1) void pi_block_kernel(PiBlock* blocks, int num_iters,
+                                                                 float tol,
+                                                                 unsigned long long timeout_ticks,
+                                                                 unsigned* expired_total) {
+  extern __shared__ __align__(16) float pi_blds[];
+  PiBlock* pb = &blocks[blockIdx.x];
+  const int n = pb->n, t = pb->t, tid = threadIdx.x;
+  if (t > PI_BLOCK_T) return;   // a team block: pi_resident_kernel
+  if (n == 0) {  // all padding: v0 masked to zero, 0/0 (DS:634)
+    if (tid == 0) {
+      pb->lambda = __uint_as_float(0x7fc00000u);
+      pb->iters = 1;
+      pb->stop_iter = 0;
+    }
+    return;
+  }
+  if (timeout_ticks == 0) {
+    // every wait counts as expired (how the tests force the recovery path): the result of a team
+    // of one whose first wait gives up -- NaN after one step, counted for the host
+    if (tid == 0) {
+      pb->s_prev = __uint_as_float(0x7fc00000u);
+      pb->lambda = __uint_as_float(0x7fc00000u);
+      pb->iters = 1;
+      pb->stop_iter = 0;
+      pb->expired = 1;
+      atomicAdd_system(expired_total, 1u);
+      __threadfence_system();
+    }
+    return;
+  }
+  float* D = pi_blds;                        // [4][kPiDiag.total] packed diagonal tiles
+  float* P = D + 4 * kPiDiag.total;          // [t][t][128] partial products of the step
+  float* vn = P + 16 * PT;                   // [t*128] iterate
+  float* wp = vn + 4 * PT;                   // [2 groups][2 buffers][4 waves][128] column partials
+  float* ysm = wp;                           // [t*128] y of the step (once the partials are summed)
+  int* rbs = reinterpret_cast<int*>(wp + 16 * PT);
+  float* red = reinterpret_cast<float*>(rbs + PT);
+  const int tp = t * PT;
+  const int g = __builtin_amdgcn_readfirstlane(tid >> 8);   // thread group: 4 wavefronts
+  const int gt = tid & 255, wave = gt >> 6, lane = tid & 63;
+  const int c4 = lane & 31, rh = lane >> 5;
+  const bool asym = *pb->asym != 0;
+  for (int j = tid; j < tp; j += 512) vn[j] = pb->vn[j];
+  if (tid < PT) rbs[tid] = pi_diag_tab.rb[tid];
+  const int noff = t * (t - 1) / 2;
+  __syncthreads();
+  if (!asym) {
+    // diagonal tiles -> packed LDS image, 16 float4 loads in flight per thread
+    const float* a = pb->a;
+    const int lda = pb->lda;
+    for (int q0 = 0; q0 < t * PT * 32; q0 += 16 * 512) {
+      f32x4 v[16];
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        const int q = q0 + u * 512 + tid;
+        const int X = q >> 12, i = (q >> 5) & 127, ch = q & 31, o = X * PT;
+        v[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (X < t && ch >= (i >> 2)) {
+          if (pb->vec_ok && o + PT <= n) {
+            v[u] = gload4(a + (int64_t)(o + i) * lda + o + 4 * ch);
+          } else if (o + i < n) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+              if (o + 4 * ch + e < n) v[u][e] = gload1(a + (int64_t)(o + i) * lda + o + 4 * ch + e);
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        const int q = q0 + u * 512 + tid;
+        const int X = q >> 12, i = (q >> 5) & 127, ch = q & 31, C = i >> 2;
+        if (X < t && ch >= C) {
+          const f32x4 s = v[u];
+          f32x4 rs;   // column 4 ch + e at position (e + C) & 3
+          switch (C & 3) {
+            case 0: rs = s; break;
+            case 1: rs = f32x4{s[3], s[0], s[1], s[2]}; break;
+            case 2: rs = f32x4{s[2], s[3], s[0], s[1]}; break;
+            default: rs = f32x4{s[1], s[2], s[3], s[0]}; break;
+          }
+          *reinterpret_cast<f32x4*>(D + X * kPiDiag.total + rbs[i] + 4 * (ch - C)) = rs;
+        }
+      }
+    }
+  }
+  // off-diagonal tiles g, g + 2, g + 4 of this group -> registers
+  f32x4 x[3][16];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int q = g + 2 * k;
+    if (q < noff) {
+      int I, J;
+      pi_offdiag_tile(t, q, I, J);
+      pi_load_tile(pb, I * PT, J * PT, wave, c4, rh, x[k]);
+    } else {
+#pragma unroll
+      for (int it = 0; it < 16; ++it) x[k][it] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+  }
+  __syncthreads();
+  const int nround = (noff + 1) / 2 > (t + 1) / 2 ? (noff + 1) / 2 : (t + 1) / 2;
+  float s_prev = 0.f;
+  for (int iter = 0; iter < num_iters; ++iter) {
+    // round k: off-diagonal tile g + 2k and (k < 2) diagonal tile g + 2k of each group
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      if (k < nround) {
+        float* wq = wp + (g * 2 + (k & 1)) * 4 * PT;   // double buffered: one barrier per round
+        const int q = g + 2 * k;
+        int I = 0, J = 0;
+        if (q < noff) {
+          pi_offdiag_tile(t, q, I, J);
+          // opaque scalars in every step (as in pi_resident_kernel): nothing derived from the tile
+          // coordinates is hoisted into VGPRs beside the 192 registers of matrix data
+          asm volatile("" : "+s"(I), "+s"(J));
+          pi_blk_offdiag(pb, x[k], I, J, t, vn, P, wq, asym, wave, c4, rh);
+        }
+        if (k < 2 && q < t) {
+          int X = q;
+          asm volatile("" : "+s"(X));
+          pi_blk_diag(pb, D + X * kPiDiag.total, X, t, vn, P, rbs, asym, wave, c4, rh);
+        }
+        __syncthreads();
+        if (q < noff && !asym && gt < PT)
+          P[(J * t + I) * PT + gt] = ((wq[gt] + wq[PT + gt]) + wq[2 * PT + gt]) + wq[3 * PT + gt];
+      }
+    }
+    __syncthreads();
+    // ---- pi_red_kernel, term for term (the same 512 threads) ----
+    float s = 0.f, ss = 0.f;
+    for (int j = tid; j < tp; j += 512) {
+      const int X = j >> 7, r = j & 127;
+      const float* p = P + X * t * PT + r;
+      float y = 0.f;
+      int Y = 0;
+      for (; Y + 4 <= t; Y += 4) {
+        const float p0 = p[(Y + 0) * PT], p1 = p[(Y + 1) * PT], p2 = p[(Y + 2) * PT],
+                    p3 = p[(Y + 3) * PT];
+        y = (((y + p0) + p1) + p2) + p3;
+      }
+      for (; Y < t; ++Y) y += p[Y * PT];
+      ysm[j] = y;
+      s += vn[j] * y;   // DS:637
+      ss += y * y;
+    }
+    s = wave_sum_f32(s);
+    ss = wave_sum_f32(ss);
+    if ((tid & 63) == 0) { red[tid >> 6] = s; red[8 + (tid >> 6)] = ss; }
+    __syncthreads();
+    float s_new = 0.f, n2 = 0.f;
+    for (int w = 0; w < 8; ++w) { s_new += red[w]; n2 += red[8 + w]; }
+    const float nrm = sqrtf(n2);
+    const bool run = fabsf(s_new - s_prev) > tol;  // DS:639
+    const bool last = iter + 1 >= num_iters;
+    for (int j = tid; j < tp; j += 512) vn[j] = j < n ? ysm[j] / nrm : 0.f;
+    __syncthreads();
+    s_prev = s_new;
+    if (!run || last) {
+      for (int j = tid; j < tp; j += 512) pb->vn[j] = vn[j];
+      if (tid == 0) {
+        pb->s_prev = s_new;
+        pb->lambda = s_new;
+        pb->iters = iter + 1;
+        pb->stop_iter = iter;
+      }
+      break;
+    }
+  }
+}
+
 // ---- host side --------------------------------------------------------------------
 struct PiPlan {
   int batch = 0, max_n = 0;
@@ -921,28 +1274,64 @@ struct PiPlan {
     g.pending = false;
   }
 
-  // Enqueues the whole iteration.  Resident execution (default): one launch per co-resident
-  // pass, matrices in registers.  Streaming execution (PS_PI_STREAMING, teams larger than the
+  // Enqueues the whole iteration.  Resident execution (default): one pi_block_kernel launch for
+  // the blocks of up to PI_BLOCK_T tiles per side, one pi_resident_kernel launch per co-resident
+  // pass of teams for the others, matrices in registers.  Streaming execution (PS_PI_STREAMING, teams larger than the
   // chip, or a resident launch in flight on another stream): 2 launches per step, fixed
   // count (data-dependent stops are taken on the device; stopped blocks' workgroups exit at
   // once).  Same arithmetic, bit-identical results.
+  // pi_block_kernel's LDS image exceeds the default dynamic-LDS limit: raised once per process.
+  static bool block_kernel_ready() {
+    static const bool ok = [] {
+      int per_cu = 0;
+      return hipFuncSetAttribute((const void*)pi_block_kernel,
+                                 hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)PI_BLOCK_LDS) == hipSuccess &&
+             hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pi_block_kernel, 512,
+                                                          PI_BLOCK_LDS) == hipSuccess &&
+             per_cu >= 1;
+    }();
+    return ok;
+  }
+
   int enqueue(hipStream_t st, int num_iters, float tol) {
     const size_t shm = 0;
     const size_t red_shm = (size_t)((max_n + PT - 1) / PT) * PT * sizeof(float);  // <= 64 KB
     if (batch == 0) return 0;
     const size_t res_lds = 2 * red_shm;
-    const int cap = (allow_resident && resident_enabled() && num_iters > 0 && res_lds <= 48 * 1024)
-                        ? resident_capacity(res_lds) : 0;
+    // Resident execution: blocks of t <= PI_BLOCK_T tiles per side get one workgroup each
+    // (pi_block_kernel, one launch, no co-residency needed), larger blocks get teams
+    // (pi_resident_kernel, co-resident passes).  Both follow the same health / gate rules.
+    bool any_small = false, any_big = false;
     int biggest = 0;
-    for (int i = 0; i < batch; ++i) biggest = std::max(biggest, team[i]);
-    const bool resident = cap > 0 && biggest <= cap && resident_acquire(st);
+    for (int i = 0; i < batch; ++i) {
+      if ((n_eff[i] + PT - 1) / PT <= PI_BLOCK_T) {
+        any_small = true;
+      } else {
+        any_big = true;
+        biggest = std::max(biggest, team[i]);
+      }
+    }
+    const bool res_ok = allow_resident && resident_enabled() && num_iters > 0;
+    const int cap = (res_ok && any_big && res_lds <= 48 * 1024) ? resident_capacity(res_lds) : 0;
+    bool teams = any_big && cap > 0 && biggest <= cap;
+    bool small = any_small && res_ok && block_kernel_ready();
+    const bool acquired = (teams || small) && resident_acquire(st);
+    teams = teams && acquired;
+    small = small && acquired;
     // granule tags must not match leftovers of an earlier call in the same workspace
-    if (resident && region_bytes) {
+    if (teams && region_bytes) {
       const hipError_t e = hipMemsetAsync(d_region, 0, region_bytes, st);
       if (e != hipSuccess) { resident_release(st); return (int)e; }
     }
     hipLaunchKernelGGL(pi_init_kernel, dim3(batch), dim3(256), 0, st, d_blocks, d_v0);
-    if (resident) {
+    if (small)   // one workgroup per block; the workgroups of team blocks return at once
+      hipLaunchKernelGGL(pi_block_kernel, dim3(batch), dim3(512), PI_BLOCK_LDS, st, d_blocks,
+                         num_iters, tol, timeout_ticks(), health().expired);
+    if (teams) {
+      std::vector<PiTeamWG> tw;   // the team workgroups of the large blocks
+      for (const PiTeamWG& w : wgs)
+        if ((n_eff[w.block] + PT - 1) / PT > PI_BLOCK_T) tw.push_back(w);
       // Passes of whole teams, in block order, at most `cap` workgroups each.  Inside a pass the
       // teams are dealt to the 8 XCDs (least loaded first, at most cap / 8 workgroups each) and the
       // per-XCD lists are interleaved -- launch index j * 8 + x runs on XCD x -- with no-op
@@ -953,26 +1342,26 @@ struct PiPlan {
       const PiTeamWG noop{-1, 0, 0, {0, 0, 0, 0}, {0, 0, 0, 0}, 0, 1};
       const int per_xcd = cap / psh::NXCD;
       size_t next = 0;
-      while (next < wgs.size()) {
-        if (team[wgs[next].block] > per_xcd) {
+      while (next < tw.size()) {
+        if (team[tw[next].block] > per_xcd) {
           // a team larger than one XCD's share of the resident slots: a pass of its own in plain
           // launch order (spread over the XCDs; it hands off through memory as before)
-          const int tm = team[wgs[next].block];
+          const int tm = team[tw[next].block];
           passes.emplace_back(launch.size(), (size_t)tm);
-          launch.insert(launch.end(), wgs.begin() + next, wgs.begin() + next + tm);
+          launch.insert(launch.end(), tw.begin() + next, tw.begin() + next + tm);
           next += tm;
           continue;
         }
         std::vector<PiTeamWG> bins[psh::NXCD];
         int used = 0;
-        while (next < wgs.size()) {
-          const int tm = team[wgs[next].block];
+        while (next < tw.size()) {
+          const int tm = team[tw[next].block];
           if (tm > per_xcd || used + tm > cap) break;
           int best = 0;
           for (int x = 1; x < psh::NXCD; ++x)
             if (bins[x].size() < bins[best].size()) best = x;
           if ((int)bins[best].size() + tm > per_xcd) break;
-          for (int m = 0; m < tm; ++m) bins[best].push_back(wgs[next + m]);
+          for (int m = 0; m < tm; ++m) bins[best].push_back(tw[next + m]);
           used += tm;
           next += tm;
         }
@@ -990,10 +1379,13 @@ struct PiPlan {
         hipLaunchKernelGGL(pi_resident_kernel<RNT>, dim3((unsigned)ps.second), dim3(256), res_lds, st,
                            d_blocks, d_wgs + ps.first, num_iters, tol, timeout_ticks(),
                            health().expired);
-      resident_release(st);
+    }
+    if (acquired) resident_release(st);
+    if ((!any_small || small) && (!any_big || teams)) {
       PS_LAUNCH_CHECK();
       return 0;
     }
+    // the rest on the streaming kernels (blocks finished above return at once in every launch)
     const int nt = (int)tiles.size();
     for (int i = 0; i < num_iters; ++i) {
       if (nt > 0)

@@ -503,7 +503,8 @@ int ps_gemm_bf16_grouped(void* stream, const ps_gemm_bf16_desc* desc, int count,
  * contiguous with `numel` float32 elements.  pgrad == NULL marks a parameter whose
  * preconditioning is skipped (precond_grad = grafting_update, DS:3557-3561).
  * diag_in/diag_out are required for Adagrad/RMSProp grafting types only; param only
- * when weight_decay != 0.  Outputs must not alias inputs of OTHER parameters;
+ * when weight_decay != 0.  numel == 0 is allowed (no pointer of such a parameter is read, all
+ * may be NULL).  Outputs must not alias inputs of OTHER parameters;
  * x_out may alias x_in of the same parameter (each element is read then written by
  * one thread). */
 typedef struct {

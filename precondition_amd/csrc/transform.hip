@@ -220,9 +220,12 @@ extern "C" int ps_transform_grads_f32(void* stream, const ps_transform_desc* des
   long long chunk0 = 0;
   for (int i = 0; i < count; ++i) {
     const ps_transform_desc& d = desc[i];
-    if (!d.grad || !d.mom_in || !d.mom_out || !d.dmom_in || !d.dmom_out || !d.upd_out ||
-        d.numel < 0 || (diag && (!d.diag_in || !d.diag_out)) ||
-        (cfg->weight_decay != 0.f && !d.param))
+    // a parameter without elements has no chunk and none of its pointers is read: an empty
+    // tensor's null data pointer is fine
+    if (d.numel < 0 ||
+        (d.numel > 0 &&
+         (!d.grad || !d.mom_in || !d.mom_out || !d.dmom_in || !d.dmom_out || !d.upd_out ||
+          (diag && (!d.diag_in || !d.diag_out)) || (cfg->weight_decay != 0.f && !d.param))))
       return PS_EINVAL;
     TParam& p = hp[i];
     p.grad = d.grad; p.pgrad = d.pgrad; p.param = d.param; p.diag_in = d.diag_in;

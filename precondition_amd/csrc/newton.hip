@@ -133,9 +133,11 @@ __device__ inline float* mi_buf(const NewtonBlock* nb, int cur) {
 }
 
 // z^(1/p) of DS:873.  One out-of-line copy, so that every kernel that initialises a try
-// (staged and persistent execution) rounds it identically.
+// (staged and persistent execution) rounds it identically.  p = 1: z^1 is z; the device powf is
+// within 1 ulp but not the identity at exponent 1 (z = 0.059479553 came back one ulp low, which the
+// reference's power does not do: tests/test_gpu_newton_exact.py, diagonal block n = 513, p = 1).
 __device__ __attribute__((noinline)) float pth_root_of_scale(float z, float inv_p) {
-  return powf(z, inv_p);
+  return inv_p == 1.f ? z : powf(z, inv_p);
 }
 
 __device__ inline float* resolve(const NewtonBlock* nb, int id, int cur) {

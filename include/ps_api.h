@@ -61,7 +61,7 @@
 extern "C" {
 #endif
 
-#define PS_VERSION 306 /* 0.3.6: ps_options grew (eigh_keep_max_cond), PS_EIGH_ACCURATE */
+#define PS_VERSION 307 /* 0.3.7: PS_DTYPE_*, ps_*_typed (bf16 gradients / parameters / updates) */
 
 enum {
   PS_OK = 0,
@@ -107,6 +107,15 @@ enum {
  * PS_SYMMETRY_ASSUME that is NOT exactly symmetric gets the root of a nearby symmetric matrix
  * without a diagnostic: use VERIFY (0.13 ms for 256 x 512^2) unless symmetry is certain. */
 enum { PS_SYMMETRY_VERIFY = 0, PS_SYMMETRY_ASSUME = 1, PS_SYMMETRY_GENERAL = 2 };
+
+/* Storage type of an operand of the ps_*_typed entry points (the every-step kernels: statistics,
+ * grouped product, transform).  A pointer field of the descriptor whose operand is declared
+ * PS_DTYPE_BF16 carries the address of bfloat16 elements (2-byte aligned, else PS_EINVAL); its
+ * leading dimensions / strides stay in ELEMENTS.  All arithmetic and every other operand stay
+ * float32: a bf16 element widens exactly, so a typed call returns the bits of the float32 entry
+ * on the promoted copy of that operand.  An unknown code is PS_EINVAL.  fp16 is not offered on
+ * purpose: the rounding and overflow of a half-precision update is a separate question. */
+enum { PS_DTYPE_F32 = 0, PS_DTYPE_BF16 = 1 };
 
 int ps_version(void);
 const char* ps_error_string(int code);
@@ -257,6 +266,15 @@ size_t ps_stats_update_grouped_workspace_bytes(const ps_stats_desc* desc, int co
 int ps_stats_update_grouped_f32(void* stream, const ps_stats_desc* desc, int count,
                                 float w1, float w2, void* workspace,
                                 size_t workspace_bytes);
+
+/* The same call with the gradient g stored as g_dtype (PS_DTYPE_*): bf16 gradients are read where
+ * they lie and widened on the way into LDS / registers; stat_in / stat_out stay float32.  Every
+ * case of the float32 form exists (both layouts, nseg > 1, k == 1, edge tiles, any 2-byte aligned
+ * base and any ld) and returns its bits on the widened gradient.  PS_DTYPE_F32 IS the float32
+ * entry.  Workspace: ps_stats_update_grouped_workspace_bytes (sizes depend on shapes only). */
+int ps_stats_update_grouped_typed(void* stream, const ps_stats_desc* desc, int count,
+                                  int g_dtype, float w1, float w2,
+                                  void* workspace, size_t workspace_bytes);
 
 /* Convenience form for one row-major [rows, cols] matrix (leading dimension ldg):
  * axis 0: S is [rows,rows] (+= g g^T);  axis 1: S is [cols,cols] (+= g^T g).
@@ -443,6 +461,22 @@ size_t ps_gemm_grouped_workspace_bytes(const ps_gemm_desc* desc, int count);
 int ps_gemm_grouped_f32(void* stream, const ps_gemm_desc* desc, int count, void* workspace,
                         size_t workspace_bytes);
 
+/* The same call with operand A of EVERY descriptor stored as a_dtype and operand B as b_dtype
+ * (c stays float32).  Supported combinations -- the ones the every-step application issues:
+ *   a_dtype  b_dtype  transa transb
+ *   F32      F32      any    any     the float32 entry itself
+ *   BF16     F32      1      0       X = g^T P (the reference orientation), incl. the one-row form
+ *                                    m = 1 whose a is a gradient vector
+ *   F32      BF16     0      0       X^T = P g (symmetric preconditioners)
+ *   BF16     F32      other          PS_EUNSUPPORTED (nothing is written)
+ *   F32      BF16     other          PS_EUNSUPPORTED
+ *   BF16     BF16     any    any     PS_EUNSUPPORTED
+ * Split-K is chosen exactly as by the float32 entry; results are its bits on the widened operand.
+ * Workspace: ps_gemm_grouped_workspace_bytes (sizes depend on shapes only). */
+int ps_gemm_grouped_typed(void* stream, const ps_gemm_desc* desc, int count,
+                          int a_dtype, int b_dtype,
+                          void* workspace, size_t workspace_bytes);
+
 /* The same grouped product as a reusable plan: the task / tile tables are built and uploaded into
  * the caller's workspace once (create), and every launch is one or two kernel launches with no
  * host-side table building.  The operand POINTERS, shapes and the workspace must stay unchanged
@@ -541,6 +575,18 @@ size_t ps_transform_grads_workspace_bytes(const ps_transform_desc* desc, int cou
 int ps_transform_grads_f32(void* stream, const ps_transform_desc* desc, int count,
                            const ps_transform_config* cfg, void* workspace,
                            size_t workspace_bytes);
+
+/* The same call with grad AND upd_out stored as grad_dtype and param as param_dtype (every
+ * combination of PS_DTYPE_F32 / PS_DTYPE_BF16 is supported; both F32 is the float32 entry).
+ * pgrad, the momenta and the diagonal statistics stay float32.  A bf16 upd_out receives the
+ * float32 update rounded to nearest even (NaN stays NaN, overflow gives infinity); mom_out,
+ * dmom_out and diag_out equal the float32 entry's on the widened inputs bit for bit.
+ * Workspace: ps_transform_grads_workspace_bytes (sizes depend on numel only). */
+int ps_transform_grads_typed(void* stream, const ps_transform_desc* desc, int count,
+                             const ps_transform_config* cfg,
+                             int grad_dtype,   /* grad AND upd_out */
+                             int param_dtype,  /* param (read only with weight decay) */
+                             void* workspace, size_t workspace_bytes);
 
 /* ---------------------------------------------------------------------------
  * Quantized optimizer state.  Replaces QuantizedValue.quantize

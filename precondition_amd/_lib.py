@@ -224,6 +224,9 @@ _SIGNATURES = {
     "ps_stats_update_grouped_f32":
         (C.c_int, [C.c_void_p, C.POINTER(StatsDesc), C.c_int, C.c_float,
                    C.c_float, C.c_void_p, C.c_size_t]),
+    "ps_stats_update_grouped_typed":
+        (C.c_int, [C.c_void_p, C.POINTER(StatsDesc), C.c_int, C.c_int, C.c_float,
+                   C.c_float, C.c_void_p, C.c_size_t]),
     "ps_stats_update_f32":
         (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                    C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_float,
@@ -258,6 +261,9 @@ _SIGNATURES = {
     "ps_gemm_grouped_workspace_bytes": (C.c_size_t, [C.POINTER(GemmDesc), C.c_int]),
     "ps_gemm_grouped_f32":
         (C.c_int, [C.c_void_p, C.POINTER(GemmDesc), C.c_int, C.c_void_p, C.c_size_t]),
+    "ps_gemm_grouped_typed":
+        (C.c_int, [C.c_void_p, C.POINTER(GemmDesc), C.c_int, C.c_int, C.c_int, C.c_void_p,
+                   C.c_size_t]),
     "ps_gemm_grouped_plan_create":
         (C.c_int, [C.c_void_p, C.POINTER(GemmDesc), C.c_int, C.c_void_p, C.c_size_t,
                    C.POINTER(C.c_void_p)]),
@@ -273,6 +279,9 @@ _SIGNATURES = {
     "ps_transform_grads_f32":
         (C.c_int, [C.c_void_p, C.POINTER(TransformDesc), C.c_int, C.POINTER(TransformConfig),
                    C.c_void_p, C.c_size_t]),
+    "ps_transform_grads_typed":
+        (C.c_int, [C.c_void_p, C.POINTER(TransformDesc), C.c_int, C.POINTER(TransformConfig),
+                   C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
     "ps_comm_unique_id": (C.c_int, [C.c_void_p]),
     "ps_comm_init": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p]),
     "ps_comm_allgather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),

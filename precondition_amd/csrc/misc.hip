@@ -5,9 +5,11 @@
 #include <vector>
 
 #include <new>
+#include <type_traits>
 
 #include "common.h"
 #include "gemm_core.hip.h"
+#include "gemm_core_widen.hip.h"
 
 using namespace psk;
 
@@ -141,6 +143,18 @@ struct GTile { int task; short tm, tn; int ks; };
 // 8 in flight per lane, rows dealt to 8 lane groups and combined through LDS in a fixed
 // order) instead of running 128 x 128 MFMA tiles with one useful row.  The ViT-B tree has 149
 // such blocks: ~1000 of the 6300 tiles of an application stage.
+// AH / BH: the operand is stored as bf16 (the pointer addresses 2-byte elements, strides in elements).
+template <bool H>
+__device__ __forceinline__ float gemv_load1(const float* p, int64_t i) {
+  if constexpr (H) return gload1h((const uint16_t*)p + i);
+  else return gload1(p + i);
+}
+template <bool H>
+__device__ __forceinline__ f32x4 gemv_load4(const float* p, int64_t i) {
+  if constexpr (H) return widen4(gload4h_raw((const uint16_t*)p + i));
+  else return gload4(p + i);
+}
+template <bool AH = false, bool BH = false>
 __device__ inline void gemv_row_tile(const float* a, int64_t astride, const float* b, int ldb,
                                      float* c, int n, int k, int col0, bool vecb, float* smem) {
   const int tid = threadIdx.x;
@@ -154,8 +168,8 @@ __device__ inline void gemv_row_tile(const float* a, int64_t astride, const floa
       float av[8];
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
-        v[u] = gload4(b + (int64_t)(kk + 8 * u) * ldb + col);
-        av[u] = gload1(a + (int64_t)(kk + 8 * u) * astride);
+        v[u] = gemv_load4<BH>(b, (int64_t)(kk + 8 * u) * ldb + col);
+        av[u] = gemv_load1<AH>(a, (int64_t)(kk + 8 * u) * astride);
       }
 #pragma unroll
       for (int u = 0; u < 8; ++u)
@@ -163,17 +177,17 @@ __device__ inline void gemv_row_tile(const float* a, int64_t astride, const floa
         for (int e = 0; e < 4; ++e) s[e] = __fmaf_rn(av[u], v[u][e], s[e]);
     }
     for (; kk < k; kk += 8) {
-      const f32x4 v = gload4(b + (int64_t)kk * ldb + col);
-      const float av = gload1(a + (int64_t)kk * astride);
+      const f32x4 v = gemv_load4<BH>(b, (int64_t)kk * ldb + col);
+      const float av = gemv_load1<AH>(a, (int64_t)kk * astride);
 #pragma unroll
       for (int e = 0; e < 4; ++e) s[e] = __fmaf_rn(av, v[e], s[e]);
     }
   } else {
     for (int kk = rg; kk < k; kk += 8) {
-      const float av = gload1(a + (int64_t)kk * astride);
+      const float av = gemv_load1<AH>(a, (int64_t)kk * astride);
 #pragma unroll
       for (int e = 0; e < 4; ++e)
-        if (col + e < n) s[e] = __fmaf_rn(av, gload1(b + (int64_t)kk * ldb + col + e), s[e]);
+        if (col + e < n) s[e] = __fmaf_rn(av, gemv_load1<BH>(b, (int64_t)kk * ldb + col + e), s[e]);
     }
   }
   float* red = smem;  // [8][128]
@@ -238,6 +252,74 @@ __global__ __launch_bounds__(256, 2) void gemm_grouped_kernel(const GTask* tasks
     return;
   }
   gemm_tile<LA, LB, GBK, true>(A, B, kext, smem, acc);
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = te.tm * TILE + acc_row(wm, i, r, lane);
+        const int col = te.tn * TILE + acc_col(wn, j, lane);
+        if (row < tk.m && col < tk.n) gstore1(out + (int64_t)row * ldo + col, acc[i][j][r]);
+      }
+}
+
+// The same tile with ONE operand stored as bf16 (ps_gemm_grouped_typed): the widening loader of
+// gemm_core_widen.hip.h writes the float32 kernel's LDS image for that operand, the other operand,
+// the K loops' tile order and the epilogues are the float32 kernel's.  GTask::a / b address 2-byte
+// elements where AH / BH says so; veca / vecb then mean "8-byte loads of four elements are legal".
+template <int LA, int LB, bool AH, bool BH>
+__global__ __launch_bounds__(256, 2) void gemm_grouped_kernel_typed(const GTask* tasks,
+                                                                    const GTile* tiles, int ntiles) {
+  static_assert(AH != BH, "exactly one bf16 operand");
+  extern __shared__ __align__(16) float smem[];
+  const GTile te = tiles[blockIdx.x];
+  if (te.task < 0) return;
+  const GTask tk = tasks[te.task];
+  const int k0 = te.ks * tk.kchunk;
+  const int kext = min(tk.kchunk, tk.k - k0);
+  const int64_t aoff = LA == KC ? (int64_t)k0 : (int64_t)k0 * tk.lda;
+  const int64_t boff = LB == KC ? (int64_t)k0 : (int64_t)k0 * tk.ldb;
+  using OpA = typename std::conditional<AH, OperandH, Operand>::type;
+  using OpB = typename std::conditional<BH, OperandH, Operand>::type;
+  using TA = typename std::conditional<AH, uint16_t, float>::type;
+  using TB = typename std::conditional<BH, uint16_t, float>::type;
+  OpA A{(const TA*)tk.a + aoff, tk.lda, te.tm * TILE, tk.m, kext, tk.veca != 0};
+  OpB B{(const TB*)tk.b + boff, tk.ldb, te.tn * TILE, tk.n, kext, tk.vecb != 0};
+  f32x16 acc[2][2];
+  float* out = tk.ksplit > 1 ? tk.partial + (int64_t)te.ks * tk.m * tk.n : tk.c;
+  const int ldo = tk.ksplit > 1 ? tk.n : tk.ldc;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  if (LB == MC && tk.m == 1 && tk.ksplit == 1) {
+    gemv_row_tile<AH, BH>(tk.a, LA == KC ? 1 : tk.lda, tk.b, tk.ldb, tk.c, tk.n, tk.k, te.tn * TILE,
+                          tk.vecb != 0, smem);
+    return;
+  }
+  const bool fast = tk.veca != 0 && tk.vecb != 0 && kext % GBK_FAST == 0 &&
+                    (te.tm + 1) * TILE <= tk.m && (te.tn + 1) * TILE <= tk.n;
+  zero_acc(acc);
+  if (fast) {
+    using LdA = typename std::conditional<AH, TileLoaderH<LA, GBK_FAST, false>, LdF32<LA, GBK_FAST, false>>::type;
+    using LdB = typename std::conditional<BH, TileLoaderH<LB, GBK_FAST, false>, LdF32<LB, GBK_FAST, false>>::type;
+    gemm_tile_accum_ld<LdA, LdB, LA, LB, GBK_FAST, true>(A, B, kext, smem, acc);
+    const int lane_off = 4 * (lane >> 5) * ldo + (lane & 31);
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        float* blk = out + (int64_t)(te.tm * TILE + wm * 64 + i * 32) * ldo + te.tn * TILE +
+                     wn * 64 + j * 32;
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          gstore1(blk + (int64_t)((r & 3) + 8 * (r >> 2)) * ldo + lane_off, acc[i][j][r]);
+      }
+    return;
+  }
+  using LgA = typename std::conditional<AH, TileLoaderH<LA, GBK, true>, LdF32<LA, GBK, true>>::type;
+  using LgB = typename std::conditional<BH, TileLoaderH<LB, GBK, true>, LdF32<LB, GBK, true>>::type;
+  gemm_tile_accum_ld<LgA, LgB, LA, LB, GBK, false>(A, B, kext, smem, acc);
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -319,11 +401,25 @@ struct ps_gemm_plan {
   GTile* dl[4] = {nullptr, nullptr, nullptr, nullptr};
   int* di[4] = {nullptr, nullptr, nullptr, nullptr};
   int ntiles[4] = {0, 0, 0, 0}, nsplit[4] = {0, 0, 0, 0};
+  int a_dtype = PS_DTYPE_F32, b_dtype = PS_DTYPE_F32;   // storage of the operands (ps_gemm_grouped_typed)
 };
+
+// 8-byte loads of four bf16 elements
+static bool vec_ok_h(const void* p, int ld) { return ((uintptr_t)p % 8 == 0) && (ld % 4 == 0); }
 
 static int gplan_build(hipStream_t st, const ps_gemm_desc* desc, int count, void* workspace,
                        size_t workspace_bytes, ps_gemm_plan& pl) {
   if (!desc || count <= 0 || !workspace) return PS_EINVAL;
+  const bool ah = pl.a_dtype == PS_DTYPE_BF16, bh = pl.b_dtype == PS_DTYPE_BF16;
+  if (ah || bh) {
+    // the instantiations that exist: A bf16 with transa = 1, transb = 0; B bf16 with transa = transb = 0
+    if (ah && bh) return PS_EUNSUPPORTED;
+    for (int i = 0; i < count; ++i) {
+      const ps_gemm_desc& d = desc[i];
+      if ((ah && ((uintptr_t)d.a % 2 != 0)) || (bh && ((uintptr_t)d.b % 2 != 0))) return PS_EINVAL;
+      if (d.transb || (ah && !d.transa) || (bh && d.transa)) return PS_EUNSUPPORTED;
+    }
+  }
   if (workspace_bytes < grouped_gemm_bytes(desc, count)) return PS_EWORKSPACE;
   std::vector<GTask> tasks[4];
   std::vector<GTile> tiles[4];
@@ -338,7 +434,8 @@ static int gplan_build(hipStream_t st, const ps_gemm_desc* desc, int count, void
       return PS_EINVAL;
     const int g = (d.transa ? 2 : 0) + (d.transb ? 1 : 0);
     GTask t{d.a, d.b, d.c, d.m, d.n, d.k, (int)d.lda, (int)d.ldb, (int)d.ldc,
-            vec_ok(d.a, (int)d.lda, 0) ? 1 : 0, vec_ok(d.b, (int)d.ldb, 0) ? 1 : 0, 1, d.k,
+            (ah ? vec_ok_h(d.a, (int)d.lda) : vec_ok(d.a, (int)d.lda, 0)) ? 1 : 0,
+            (bh ? vec_ok_h(d.b, (int)d.ldb) : vec_ok(d.b, (int)d.ldb, 0)) ? 1 : 0, 1, d.k,
             nullptr};
     const int s = splitk_for(total_tiles, d.k);
     if (s > 1) {
@@ -393,8 +490,10 @@ static int gplan_build(hipStream_t st, const ps_gemm_desc* desc, int count, void
     PS_RC(psh::upload_async(st, pl.di[g], split_ids[g].data(), sizeof(int) * split_ids[g].size()));
   }
   static const bool lds_ok = [] {
-    const void* ks[4] = {(const void*)gemm_grouped_kernel<KC, MC>, (const void*)gemm_grouped_kernel<KC, KC>,
-                         (const void*)gemm_grouped_kernel<MC, MC>, (const void*)gemm_grouped_kernel<MC, KC>};
+    const void* ks[6] = {(const void*)gemm_grouped_kernel<KC, MC>, (const void*)gemm_grouped_kernel<KC, KC>,
+                         (const void*)gemm_grouped_kernel<MC, MC>, (const void*)gemm_grouped_kernel<MC, KC>,
+                         (const void*)gemm_grouped_kernel_typed<MC, MC, true, false>,
+                         (const void*)gemm_grouped_kernel_typed<KC, MC, false, true>};
     for (const void* k : ks)
       (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 GEMM_GROUPED_LDS_BYTES);
@@ -406,6 +505,23 @@ static int gplan_build(hipStream_t st, const ps_gemm_desc* desc, int count, void
 
 static int gplan_launch(hipStream_t st, const ps_gemm_plan& pl) {
   const dim3 blk(256);
+  if (pl.a_dtype == PS_DTYPE_BF16 || pl.b_dtype == PS_DTYPE_BF16) {
+    // gplan_build admitted one layout group: 2 (transa = 1, A bf16) or 0 (transa = transb = 0, B bf16)
+    const int G = pl.a_dtype == PS_DTYPE_BF16 ? 2 : 0;
+    if (pl.ntiles[G] > 0) {
+      if (G == 2)
+        hipLaunchKernelGGL((gemm_grouped_kernel_typed<MC, MC, true, false>), dim3((unsigned)pl.ntiles[G]),
+                           blk, GEMM_GROUPED_LDS_BYTES, st, pl.dt[G], pl.dl[G], pl.ntiles[G]);
+      else
+        hipLaunchKernelGGL((gemm_grouped_kernel_typed<KC, MC, false, true>), dim3((unsigned)pl.ntiles[G]),
+                           blk, GEMM_GROUPED_LDS_BYTES, st, pl.dt[G], pl.dl[G], pl.ntiles[G]);
+      if (pl.nsplit[G] > 0)
+        hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3((unsigned)pl.nsplit[G], 256), blk, 0, st,
+                           pl.dt[G], pl.di[G]);
+    }
+    PS_LAUNCH_CHECK();
+    return PS_OK;
+  }
 #define PS_GG(G, LA, LB)                                                                   \
   if (pl.ntiles[G] > 0) {                                                                  \
     hipLaunchKernelGGL((gemm_grouped_kernel<LA, LB>), dim3((unsigned)pl.ntiles[G]), blk,   \
@@ -427,6 +543,19 @@ extern "C" int ps_gemm_grouped_f32(void* stream, const ps_gemm_desc* desc, int c
                                    void* workspace, size_t workspace_bytes) {
   PS_DEVICE_CHECK();
   ps_gemm_plan pl;
+  PS_RC(gplan_build((hipStream_t)stream, desc, count, workspace, workspace_bytes, pl));
+  return gplan_launch((hipStream_t)stream, pl);
+}
+
+extern "C" int ps_gemm_grouped_typed(void* stream, const ps_gemm_desc* desc, int count, int a_dtype,
+                                     int b_dtype, void* workspace, size_t workspace_bytes) {
+  if ((a_dtype != PS_DTYPE_F32 && a_dtype != PS_DTYPE_BF16) ||
+      (b_dtype != PS_DTYPE_F32 && b_dtype != PS_DTYPE_BF16))
+    return PS_EINVAL;
+  PS_DEVICE_CHECK();
+  ps_gemm_plan pl;
+  pl.a_dtype = a_dtype;
+  pl.b_dtype = b_dtype;
   PS_RC(gplan_build((hipStream_t)stream, desc, count, workspace, workspace_bytes, pl));
   return gplan_launch((hipStream_t)stream, pl);
 }

@@ -20,6 +20,7 @@
 
 #include "common.h"
 #include "gemm_core.hip.h"
+#include "gemm_core_widen.hip.h"
 
 namespace psk {
 
@@ -127,11 +128,30 @@ __device__ inline void stats_store_mirror_v4(const f32x16 (&acc)[2][2], float* s
   }
 }
 
-template <int LAYOUT, bool FAST>
+// H: the gradient is stored as bf16 (tk.g points at 2-byte elements, ld / seg_stride in elements):
+// the widening loader writes the float32 kernel's LDS image, everything after it is shared.
+template <int LAYOUT, bool FAST, bool H = false>
 __device__ __forceinline__ void stats_tile(const StatsTask& tk, int tm, int tn, float w1,
                                            float w2, float* smem) {
   f32x16 acc[2][2];
   zero_acc(acc);
+  if constexpr (H) {
+    using Ld = TileLoaderH<LAYOUT, SBK, !FAST>;
+    const uint16_t* g = (const uint16_t*)tk.g;
+    if (tk.nseg == 1) {   // as below: the two-set pipeline stays outside the segment loop
+      OperandH A{g, tk.ld, tm * TILE, tk.d, tk.k, tk.vec != 0};
+      OperandH B{g, tk.ld, tn * TILE, tk.d, tk.k, tk.vec != 0};
+      gemm_tile_accum_ld<Ld, Ld, LAYOUT, LAYOUT, SBK, FAST>(A, B, tk.k, smem, acc);
+    } else {
+#pragma unroll 1
+      for (int s = 0; s < tk.nseg; ++s) {
+        const uint16_t* base = g + (int64_t)s * tk.seg_stride;
+        OperandH A{base, tk.ld, tm * TILE, tk.d, tk.k, tk.vec != 0};
+        OperandH B{base, tk.ld, tn * TILE, tk.d, tk.k, tk.vec != 0};
+        gemm_tile_accum_ld<Ld, Ld, LAYOUT, LAYOUT, SBK, false>(A, B, tk.k, smem, acc);
+      }
+    }
+  } else
   // nseg == 1 (every matrix-shaped block) outside the segment loop: the loop around the
   // two-register-set pipeline costs ~100 spilled VGPRs, which only rank>2 blocks then pay
   if (tk.nseg == 1) {
@@ -195,13 +215,20 @@ __device__ __forceinline__ bool stats_tile_is_fast(const StatsTask& tk, int tm, 
   return tk.fast != 0 && tk.svec != 0 && (tn + 1) * TILE <= tk.d && (tm + 1) * TILE <= tk.d;
 }
 
-template <int LAYOUT>
+template <int LAYOUT, bool H = false>
 __device__ __forceinline__ void stats_tile_any(const StatsTask& tk, int tm, int tn, float w1,
                                                float w2, float* smem) {
   if (stats_tile_is_fast(tk, tm, tn))
-    stats_tile<LAYOUT, true>(tk, tm, tn, w1, w2, smem);
+    stats_tile<LAYOUT, true, H>(tk, tm, tn, w1, w2, smem);
   else
-    stats_tile<LAYOUT, false>(tk, tm, tn, w1, w2, smem);
+    stats_tile<LAYOUT, false, H>(tk, tm, tn, w1, w2, smem);
+}
+
+// element i of the gradient as float32 (H: stored as bf16)
+template <bool H>
+__device__ __forceinline__ float stats_gload(const float* g, int64_t i) {
+  if constexpr (H) return gload1h((const uint16_t*)g + i);
+  else return gload1(g + i);
 }
 
 // Statistic of a vector block (k = 1: biases, scales): S = w1*S + w2 * g g^T is one product per
@@ -209,6 +236,7 @@ __device__ __forceinline__ void stats_tile_any(const StatsTask& tk, int tm, int 
 // streamed by the VALU (16-byte accesses where the statistic allows them) without the LDS
 // pipeline.  Writes the 128x128 tile at (rt, ct); the caller passes both orders of an
 // off-diagonal pair.  A ViT-B tree holds 149 such statistics, 0.85 GB of read + write.
+template <bool H = false>
 __device__ inline void stats_vector_tile(const StatsTask& tk, int rt, int ct, float w1,
                                          float w2) {
   const int tid = threadIdx.x;
@@ -217,7 +245,7 @@ __device__ inline void stats_vector_tile(const StatsTask& tk, int rt, int ct, fl
   float gc[4];
 #pragma unroll
   for (int e = 0; e < 4; ++e)
-    gc[e] = c + e < tk.d ? gload1(tk.g + (int64_t)(c + e) * estride) : 0.f;
+    gc[e] = c + e < tk.d ? stats_gload<H>(tk.g, (int64_t)(c + e) * estride) : 0.f;
   const bool v4 = tk.svec != 0 && c + 3 < tk.d;
   if (v4 && (rt + 1) * TILE <= tk.d) {
     // whole rows in range: 8 loads in flight per lane (the workgroup count per CU is set by
@@ -229,7 +257,7 @@ __device__ inline void stats_vector_tile(const StatsTask& tk, int rt, int ct, fl
 #pragma unroll
       for (int p = 0; p < 8; ++p) {
         const int r = rt * TILE + (half * 8 + p) * 8 + (tid >> 5);
-        gr[p] = gload1(tk.g + (int64_t)r * estride);
+        gr[p] = stats_gload<H>(tk.g, (int64_t)r * estride);
         old[p] = gload4(tk.sin + (int64_t)r * tk.lds + c);
       }
 #pragma unroll
@@ -248,7 +276,7 @@ __device__ inline void stats_vector_tile(const StatsTask& tk, int rt, int ct, fl
   for (int p = 0; p < 16; ++p) {
     const int r = rt * TILE + p * 8 + (tid >> 5);
     if (r >= tk.d) break;
-    const float gr = gload1(tk.g + (int64_t)r * estride);
+    const float gr = stats_gload<H>(tk.g, (int64_t)r * estride);
     const int64_t o = (int64_t)r * tk.lds + c;
     if (v4) {
       const f32x4 old = gload4(tk.sin + o);
@@ -288,6 +316,25 @@ __global__ __launch_bounds__(256, 2) void stats_grouped_kernel(const StatsTask* 
   }
 }
 
+// The same launch for a tree whose gradients are stored as bf16 (ps_stats_update_grouped_typed).
+__global__ __launch_bounds__(256, 2) void stats_grouped_kernel_bf16(const StatsTask* tasks,
+                                                                    const StatsTile* tiles,
+                                                                    int ntiles, float w1,
+                                                                    float w2) {
+  extern __shared__ __align__(16) float smem[];
+  const StatsTile te = tiles[blockIdx.x];
+  if (te.task < 0) return;
+  const StatsTask tk = tasks[te.task];
+  if (tk.k == 1 && tk.nseg == 1) {
+    stats_vector_tile<true>(tk, te.tm, te.tn, w1, w2);
+    if (te.tm != te.tn) stats_vector_tile<true>(tk, te.tn, te.tm, w1, w2);
+  } else if (tk.layout == KC) {
+    stats_tile_any<KC, true>(tk, te.tm, te.tn, w1, w2, smem);
+  } else {
+    stats_tile_any<MC, true>(tk, te.tm, te.tn, w1, w2, smem);
+  }
+}
+
 template <int LAYOUT>
 __global__ __launch_bounds__(256, 2) void stats_single_kernel(StatsTask tk, int tiles_n,
                                                               float w1, float w2) {
@@ -305,7 +352,7 @@ namespace {
 
 using psh::NXCD;
 
-bool to_task(const ps_stats_desc& d, StatsTask& t) {
+bool to_task(const ps_stats_desc& d, StatsTask& t, bool h = false) {
   if (!d.g || !d.stat_in || !d.stat_out || d.d < 1 || d.k < 1 || d.nseg < 1 ||
       (d.layout != 0 && d.layout != 1) || d.lds < d.d || d.ld < 1 ||
       d.ld > 0x7fffffff || d.lds > 0x7fffffff)
@@ -315,7 +362,9 @@ bool to_task(const ps_stats_desc& d, StatsTask& t) {
   t.g = d.g; t.sin = d.stat_in; t.sout = d.stat_out;
   t.seg_stride = d.seg_stride;
   t.d = d.d; t.k = d.k; t.ld = (int)d.ld; t.lds = (int)d.lds; t.nseg = d.nseg;
-  t.vec = ((uintptr_t)d.g % 16 == 0) && (d.ld % 4 == 0) && (d.seg_stride % 4 == 0);
+  // vector loads of four elements: 16 bytes of float32, 8 bytes of bf16
+  if (h && (uintptr_t)d.g % 2 != 0) return false;
+  t.vec = ((uintptr_t)d.g % (h ? 8 : 16) == 0) && (d.ld % 4 == 0) && (d.seg_stride % 4 == 0);
   t.fast = t.vec && d.k % SBK == 0;
   t.svec = (uintptr_t)d.stat_in % 16 == 0 && (uintptr_t)d.stat_out % 16 == 0 && d.lds % 4 == 0;
   t.layout = d.layout;
@@ -369,6 +418,7 @@ void allow_lds(K kernel) {
 void stats_lds_once() {
   static const bool done = [] {
     allow_lds(stats_grouped_kernel);
+    allow_lds(stats_grouped_kernel_bf16);
     allow_lds(stats_single_kernel<KC>);
     allow_lds(stats_single_kernel<MC>);
     return true;
@@ -384,9 +434,8 @@ extern "C" size_t ps_stats_update_grouped_workspace_bytes(const ps_stats_desc* d
   return grouped_bytes(desc, count);
 }
 
-extern "C" int ps_stats_update_grouped_f32(void* stream, const ps_stats_desc* desc,
-                                           int count, float w1, float w2,
-                                           void* workspace, size_t workspace_bytes) {
+static int stats_update_grouped(void* stream, const ps_stats_desc* desc, int count, bool h,
+                                float w1, float w2, void* workspace, size_t workspace_bytes) {
   PS_DEVICE_CHECK();
   if (!desc || count <= 0 || !workspace) return PS_EINVAL;
   if (workspace_bytes < grouped_bytes(desc, count)) return PS_EWORKSPACE;
@@ -394,7 +443,7 @@ extern "C" int ps_stats_update_grouped_f32(void* stream, const ps_stats_desc* de
   stats_lds_once();
   std::vector<StatsTask> tasks(count);
   for (int i = 0; i < count; ++i)
-    if (!to_task(desc[i], tasks[i])) return PS_EINVAL;
+    if (!to_task(desc[i], tasks[i], h)) return PS_EINVAL;
   std::vector<StatsTile> tiles;
   make_tile_list(tasks, tiles);
   // one staging buffer, one H2D copy: [tasks][tiles]
@@ -408,11 +457,30 @@ extern "C" int ps_stats_update_grouped_f32(void* stream, const ps_stats_desc* de
   memcpy(plan.data() + task_bytes, tiles.data(), tile_bytes);
   PS_RC(psh::upload_async(st, d_plan, plan.data(), plan.size()));
   const int nt = (int)tiles.size();
-  hipLaunchKernelGGL(stats_grouped_kernel, dim3(nt), dim3(256), STATS_LDS_BYTES, st,
-                     (const StatsTask*)d_plan, (const StatsTile*)(d_plan + task_bytes), nt, w1,
-                     w2);
+  if (h)
+    hipLaunchKernelGGL(stats_grouped_kernel_bf16, dim3(nt), dim3(256), STATS_LDS_BYTES, st,
+                       (const StatsTask*)d_plan, (const StatsTile*)(d_plan + task_bytes), nt, w1,
+                       w2);
+  else
+    hipLaunchKernelGGL(stats_grouped_kernel, dim3(nt), dim3(256), STATS_LDS_BYTES, st,
+                       (const StatsTask*)d_plan, (const StatsTile*)(d_plan + task_bytes), nt, w1,
+                       w2);
   PS_LAUNCH_CHECK();
   return PS_OK;
+}
+
+extern "C" int ps_stats_update_grouped_f32(void* stream, const ps_stats_desc* desc,
+                                           int count, float w1, float w2,
+                                           void* workspace, size_t workspace_bytes) {
+  return stats_update_grouped(stream, desc, count, false, w1, w2, workspace, workspace_bytes);
+}
+
+extern "C" int ps_stats_update_grouped_typed(void* stream, const ps_stats_desc* desc, int count,
+                                             int g_dtype, float w1, float w2, void* workspace,
+                                             size_t workspace_bytes) {
+  if (g_dtype != PS_DTYPE_F32 && g_dtype != PS_DTYPE_BF16) return PS_EINVAL;
+  return stats_update_grouped(stream, desc, count, g_dtype == PS_DTYPE_BF16, w1, w2, workspace,
+                              workspace_bytes);
 }
 
 extern "C" int ps_stats_update_f32(void* stream, const float* g, int64_t rows,

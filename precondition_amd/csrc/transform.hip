@@ -75,9 +75,28 @@ __device__ inline float param_sum(const float* slab, int col, const TParam& p, f
   return block_sum(s, red);
 }
 
+// Storage of grad / upd_out (GH) and of param (PH): float32, or bf16 behind the same pointer
+// fields (ps_transform_grads_typed).  A bf16 element widens exactly; the update is rounded to
+// nearest even from the float32 value the float32 kernel stores.
+template <bool H>
+__device__ __forceinline__ float tload(const float* p, int64_t i) {
+  if constexpr (H) return __uint_as_float((uint32_t)(*(const uint16_t PS_GLOBAL*)((const uint16_t*)p + i)) << 16);
+  else return gload1(p + i);
+}
+template <bool H>
+__device__ __forceinline__ void tstore(float* p, int64_t i, float v) {
+  if constexpr (H) {
+    const __bf16 h = (__bf16)v;
+    *(uint16_t PS_GLOBAL*)((uint16_t*)p + i) = __builtin_bit_cast(uint16_t, h);
+  } else {
+    gstore1(p + i, v);
+  }
+}
+
 // pass A: slab[.][0] = sum (graft base)^2 ; slab[.][1] = sum pgrad^2
-__global__ __launch_bounds__(256) void transform_pass_a(const TParam* params, int count,
-                                                        float* slab, ps_transform_config cfg) {
+template <bool GH>
+__device__ __forceinline__ void transform_pass_a_body(const TParam* params, int count,
+                                                      float* slab, const ps_transform_config& cfg) {
   __shared__ float red[4];
   const TChunk ch = find_chunk(params, count, blockIdx.x);
   const TParam p = params[ch.param];
@@ -85,7 +104,7 @@ __global__ __launch_bounds__(256) void transform_pass_a(const TParam* params, in
   const int64_t hi = lo + TCHUNK < p.numel ? lo + TCHUNK : p.numel;
   float s0 = 0.f, s1 = 0.f;
   for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
-    const float g = gload1(p.grad + i);
+    const float g = tload<GH>(p.grad, i);
     float base = g;
     if (cfg.graft_type == G_SQRT_N) base = g > 0.f ? 1.f : (g < 0.f ? -1.f : 0.f);
     s0 += base * base;
@@ -99,6 +118,15 @@ __global__ __launch_bounds__(256) void transform_pass_a(const TParam* params, in
   }
 }
 
+__global__ __launch_bounds__(256) void transform_pass_a(const TParam* params, int count,
+                                                        float* slab, ps_transform_config cfg) {
+  transform_pass_a_body<false>(params, count, slab, cfg);
+}
+__global__ __launch_bounds__(256) void transform_pass_a_bf16(const TParam* params, int count,
+                                                             float* slab, ps_transform_config cfg) {
+  transform_pass_a_body<true>(params, count, slab, cfg);
+}
+
 // Diagonal grafting update before lr / clipping (DS:3502-3528).
 __device__ inline float diag_graft(float g, float gden, float diag, int graft, float w1,
                                    float w2, float eps, float& new_diag) {
@@ -109,8 +137,9 @@ __device__ inline float diag_graft(float g, float gden, float diag, int graft, f
 }
 
 // pass B (Adagrad/RMSProp only): slab[.][2] = sum u^2 of the unclipped update
-__global__ __launch_bounds__(256) void transform_pass_b(const TParam* params, int count,
-                                                        float* slab, ps_transform_config cfg) {
+template <bool GH>
+__device__ __forceinline__ void transform_pass_b_body(const TParam* params, int count,
+                                                      float* slab, const ps_transform_config& cfg) {
   __shared__ float red[4];
   const TChunk ch = find_chunk(params, count, blockIdx.x);
   const TParam p = params[ch.param];
@@ -121,7 +150,7 @@ __global__ __launch_bounds__(256) void transform_pass_b(const TParam* params, in
   float s = 0.f;
   for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
     float nd;
-    const float u = diag_graft(gload1(p.grad + i), gscale, gload1(p.diag_in + i), cfg.graft_type,
+    const float u = diag_graft(tload<GH>(p.grad, i), gscale, gload1(p.diag_in + i), cfg.graft_type,
                                cfg.beta2_w1, cfg.beta2_w2, cfg.diagonal_epsilon, nd);
     s += u * u;
   }
@@ -129,9 +158,19 @@ __global__ __launch_bounds__(256) void transform_pass_b(const TParam* params, in
   if (threadIdx.x == 0) slab[(int64_t)(p.chunk0 + ch.idx) * 4 + 2] = s;
 }
 
+__global__ __launch_bounds__(256) void transform_pass_b(const TParam* params, int count,
+                                                        float* slab, ps_transform_config cfg) {
+  transform_pass_b_body<false>(params, count, slab, cfg);
+}
+__global__ __launch_bounds__(256) void transform_pass_b_bf16(const TParam* params, int count,
+                                                             float* slab, ps_transform_config cfg) {
+  transform_pass_b_body<true>(params, count, slab, cfg);
+}
+
 // pass C: everything else, elementwise
-__global__ __launch_bounds__(256) void transform_pass_c(const TParam* params, int count,
-                                                        const float* slab, ps_transform_config cfg) {
+template <bool GH, bool PH>
+__device__ __forceinline__ void transform_pass_c_body(const TParam* params, int count,
+                                                      const float* slab, const ps_transform_config& cfg) {
   __shared__ float red[4];
   const TChunk ch = find_chunk(params, count, blockIdx.x);
   const TParam p = params[ch.param];
@@ -163,7 +202,7 @@ __global__ __launch_bounds__(256) void transform_pass_c(const TParam* params, in
   const int64_t lo = (int64_t)ch.idx * TCHUNK;
   const int64_t hi = lo + TCHUNK < p.numel ? lo + TCHUNK : p.numel;
   for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
-    const float g = gload1(p.grad + i);
+    const float g = tload<GH>(p.grad, i);
     float gu;
     if (has_diag(graft)) {
       float nd;
@@ -180,7 +219,7 @@ __global__ __launch_bounds__(256) void transform_pass_c(const TParam* params, in
     const float pg = p.pgrad ? gload1(p.pgrad + i) : gu;
     float su = pg * mult;  // shampoo_update
     float sw = su, gw = gu;
-    const float prm = (coupled_wd || dec_wd) ? gload1(p.param + i) : 0.f;
+    const float prm = (coupled_wd || dec_wd) ? tload<PH>(p.param, i) : 0.f;
     if (coupled_wd) { sw = su + cfg.weight_decay * prm; gw = gu + cfg.weight_decay * prm; }
     const float smom = gload1(p.mom_in + i) * cfg.beta1 + w * sw;    // DS:3581-3586
     const float gmom = gload1(p.dmom_in + i) * cfg.beta1 + w * gw;
@@ -189,10 +228,21 @@ __global__ __launch_bounds__(256) void transform_pass_c(const TParam* params, in
     float nest = mom_u;
     if (cfg.nesterov) nest = w * wd_u + cfg.beta1 * mom_u;           // DS:3601-3602
     if (dec_wd) nest = nest + wd_lr * cfg.weight_decay * prm;
-    gstore1(p.upd_out + i, -1.f * mm * nest);
+    tstore<GH>(p.upd_out, i, -1.f * mm * nest);
     gstore1(p.mom_out + i, smom);
     gstore1(p.dmom_out + i, gmom);
   }
+}
+
+__global__ __launch_bounds__(256) void transform_pass_c(const TParam* params, int count,
+                                                        const float* slab, ps_transform_config cfg) {
+  transform_pass_c_body<false, false>(params, count, slab, cfg);
+}
+// <storage of grad / upd_out, storage of param>
+template <bool GH, bool PH>
+__global__ __launch_bounds__(256) void transform_pass_c_typed(const TParam* params, int count,
+                                                              const float* slab, ps_transform_config cfg) {
+  transform_pass_c_body<GH, PH>(params, count, slab, cfg);
 }
 
 }  // namespace psk
@@ -207,9 +257,9 @@ extern "C" size_t ps_transform_grads_workspace_bytes(const ps_transform_desc* de
          psh::align_up(sizeof(float) * 4 * chunks, 256) + 1024;
 }
 
-extern "C" int ps_transform_grads_f32(void* stream, const ps_transform_desc* desc, int count,
-                                      const ps_transform_config* cfg, void* workspace,
-                                      size_t workspace_bytes) {
+static int transform_grads(void* stream, const ps_transform_desc* desc, int count,
+                           const ps_transform_config* cfg, bool gh, bool ph, void* workspace,
+                           size_t workspace_bytes) {
   PS_DEVICE_CHECK();
   if (!desc || !cfg || count <= 0 || !workspace) return PS_EINVAL;
   if (workspace_bytes < ps_transform_grads_workspace_bytes(desc, count)) return PS_EWORKSPACE;
@@ -226,6 +276,9 @@ extern "C" int ps_transform_grads_f32(void* stream, const ps_transform_desc* des
         (d.numel > 0 &&
          (!d.grad || !d.mom_in || !d.mom_out || !d.dmom_in || !d.dmom_out || !d.upd_out ||
           (diag && (!d.diag_in || !d.diag_out)) || (cfg->weight_decay != 0.f && !d.param))))
+      return PS_EINVAL;
+    if (d.numel > 0 && ((gh && ((uintptr_t)d.grad % 2 != 0 || (uintptr_t)d.upd_out % 2 != 0)) ||
+                        (ph && (uintptr_t)d.param % 2 != 0)))
       return PS_EINVAL;
     TParam& p = hp[i];
     p.grad = d.grad; p.pgrad = d.pgrad; p.param = d.param; p.diag_in = d.diag_in;
@@ -245,9 +298,41 @@ extern "C" int ps_transform_grads_f32(void* stream, const ps_transform_desc* des
   if (ar.overflow) return PS_EWORKSPACE;
   PS_RC(psh::upload_async(st, dp, hp.data(), sizeof(TParam) * count));
   const dim3 grid((unsigned)chunk0), blk(256);
-  hipLaunchKernelGGL(transform_pass_a, grid, blk, 0, st, dp, count, slab, *cfg);
-  if (diag) hipLaunchKernelGGL(transform_pass_b, grid, blk, 0, st, dp, count, slab, *cfg);
-  hipLaunchKernelGGL(transform_pass_c, grid, blk, 0, st, dp, count, slab, *cfg);
+  if (!gh && !ph) {
+    hipLaunchKernelGGL(transform_pass_a, grid, blk, 0, st, dp, count, slab, *cfg);
+    if (diag) hipLaunchKernelGGL(transform_pass_b, grid, blk, 0, st, dp, count, slab, *cfg);
+    hipLaunchKernelGGL(transform_pass_c, grid, blk, 0, st, dp, count, slab, *cfg);
+  } else {
+    if (gh) {
+      hipLaunchKernelGGL(transform_pass_a_bf16, grid, blk, 0, st, dp, count, slab, *cfg);
+      if (diag) hipLaunchKernelGGL(transform_pass_b_bf16, grid, blk, 0, st, dp, count, slab, *cfg);
+    } else {
+      hipLaunchKernelGGL(transform_pass_a, grid, blk, 0, st, dp, count, slab, *cfg);
+      if (diag) hipLaunchKernelGGL(transform_pass_b, grid, blk, 0, st, dp, count, slab, *cfg);
+    }
+    if (gh && ph)
+      hipLaunchKernelGGL((transform_pass_c_typed<true, true>), grid, blk, 0, st, dp, count, slab, *cfg);
+    else if (gh)
+      hipLaunchKernelGGL((transform_pass_c_typed<true, false>), grid, blk, 0, st, dp, count, slab, *cfg);
+    else
+      hipLaunchKernelGGL((transform_pass_c_typed<false, true>), grid, blk, 0, st, dp, count, slab, *cfg);
+  }
   PS_LAUNCH_CHECK();
   return PS_OK;
+}
+
+extern "C" int ps_transform_grads_f32(void* stream, const ps_transform_desc* desc, int count,
+                                      const ps_transform_config* cfg, void* workspace,
+                                      size_t workspace_bytes) {
+  return transform_grads(stream, desc, count, cfg, false, false, workspace, workspace_bytes);
+}
+
+extern "C" int ps_transform_grads_typed(void* stream, const ps_transform_desc* desc, int count,
+                                        const ps_transform_config* cfg, int grad_dtype,
+                                        int param_dtype, void* workspace, size_t workspace_bytes) {
+  if ((grad_dtype != PS_DTYPE_F32 && grad_dtype != PS_DTYPE_BF16) ||
+      (param_dtype != PS_DTYPE_F32 && param_dtype != PS_DTYPE_BF16))
+    return PS_EINVAL;
+  return transform_grads(stream, desc, count, cfg, grad_dtype == PS_DTYPE_BF16,
+                         param_dtype == PS_DTYPE_BF16, workspace, workspace_bytes);
 }

@@ -167,7 +167,9 @@ def distributed_shampoo(
     # returned state holds the same tensors, and the returned updates live in buffers the optimizer
     # owns (valid until the next update call) -- no allocation, no descriptor rebuilt, the same
     # seven launches (plan.DonatedStep).  The state passed in must not be used afterwards.  Applies
-    # to float32 dense states (the tree-plan path); anything else takes the functional path.
+    # to dense states (the tree-plan path; the state itself is float32) with gradients that are
+    # uniformly float32 or uniformly bfloat16 -- the latter are read where they lie and the updates
+    # come back in bfloat16; anything else takes the functional path.
     donate_state: bool = False,
     _backend_for_testing: Any = None,
 ):
@@ -229,8 +231,9 @@ def distributed_shampoo(
     raise NotImplementedError("shard_statistics supports the dense preconditioner mode")
 
   def _zeros_f32_like(param):
-    """State buffers are float32 whatever the parameter dtype (the kernels take float32 only;
-    bf16 / fp16 parameters and gradients are promoted at the door of update())."""
+    """State buffers are float32 whatever the parameter dtype.  A tree of contiguous bfloat16
+    gradients (and bfloat16 parameters) on the tree-plan path is read natively by the every-step
+    kernels; fp16, mixed trees and the general per-block path are promoted at the door of update()."""
     return torch.zeros_like(param, dtype=torch.float32)
 
   def _owned_mask(params_flat):
@@ -435,6 +438,16 @@ def distributed_shampoo(
     return ShampooState(count=torch.zeros([], dtype=torch.int32), stats=stats)
 
   # ---------------------------------------------------------------------------
+  def _promoted(tensors):
+    return [t if t.dtype == torch.float32 else t.to(torch.float32) for t in tensors]
+
+  def _native_bf16(grads_flat, params_flat):
+    """Does this step read its gradients as bfloat16 where they lie?  A tree of contiguous bfloat16
+    CUDA gradients that has a tree plan, on a backend that declares the capability."""
+    return (getattr(backend, "NATIVE_BF16_GRADIENTS", False) and len(grads_flat) > 0 and
+            all(g.dtype == torch.bfloat16 and g.is_cuda and g.is_contiguous() for g in grads_flat)
+            and _tree_plan(params_flat) is not None)
+
   def _compute_stats_all(grads_flat, stats_flat, params_flat, step):
     """DS:2631-2675 for every parameter, as ONE grouped Gram launch."""
     w1 = beta2
@@ -468,6 +481,7 @@ def distributed_shampoo(
                                     st.training_metrics))
           k += cnt
         return out
+    grads_flat = _promoted(grads_flat)   # the per-block path reads float32
     new_lists, items, fd_items, new_avg = [], [], [], []
     owned = _owned_mask(params_flat) if shard_stats else None
     float_old = None
@@ -802,13 +816,14 @@ def distributed_shampoo(
     plan = _tree_plan(params_flat)
     if plan is not None and all(g.is_contiguous() for g in grads_flat):
       precs_flat = [p for st in states for p in st.preconditioners]
+      out_f32 = lambda g: torch.empty(g.shape, dtype=torch.float32, device=g.device)
       if quantize_second_moment:  # _maybe_dequantize_preconditioners, DS:2097-2106
         precs_flat = _to_float_many(precs_flat)
       if len(precs_flat) == len(plan.stat_dims) and all(
           p.is_contiguous() and p.dtype == torch.float32 for p in precs_flat):
         for i, (g, sk) in enumerate(zip(grads_flat, plan.skipped)):
           if not sk:
-            out[i] = torch.empty_like(g)
+            out[i] = out_f32(g)   # float32 whatever the gradient's dtype
         # (dequantized int16 preconditioners are column-scaled, not exactly symmetric: they keep
         # the reference's operand orientation)
         # Precondition of the symmetric operand layout (P_L g applied as P_L^T g): float32 roots of
@@ -821,6 +836,7 @@ def distributed_shampoo(
                                    symmetric_precs=(not quantize_second_moment and
                                                     not lobpcg_topk_precondition))
         return out
+    grads_flat = _promoted(grads_flat)   # the per-block path reads float32
     stage_a, stage_b, keep = [], [], []
     precs = [st.preconditioners for st in states]
     if quantize_second_moment:  # _maybe_dequantize_preconditioners, DS:2097-2106
@@ -977,12 +993,13 @@ def distributed_shampoo(
       from .plan import DonatedStep
       ds = _donated[id(plan)] = DonatedStep(plan, _graft_type_has_diagonal_statistics(),
                                             weight_decay != 0)
-    if not ds.bound_to(stats_flat):
+    gdt = grads_flat[0].dtype
+    if not ds.bound_to(stats_flat) or ds.gdtype != gdt:   # (a change of gradient dtype binds again)
       ok = (all(isinstance(st, ParameterStats) and
                 st.momentum.quantized_dtype == torch.float32 and
                 st.diagonal_momentum.quantized_dtype == torch.float32 and
                 isinstance(st.avg_grad, MaskedNode) for st in stats_flat) and
-            all(g.dtype == torch.float32 and g.is_contiguous() for g in grads_flat))
+            all(g.dtype == gdt and g.is_contiguous() for g in grads_flat))
       if not ok or not ds.bind(stats_flat, grads_flat, params_flat, symmetric_precs=True):
         return None
     if not ds.qualifies(grads_flat, params_flat):   # every step: strides / dtype / device / shape
@@ -1025,6 +1042,20 @@ def distributed_shampoo(
                                        s.training_metrics)))
     return outs
 
+  def _at_the_door(grads_flat, params_flat, native_bf16):
+    """Gradients and parameters as the kernels read them: float32 copies, or -- native_bf16 -- the
+    bfloat16 gradients themselves and parameters that are uniformly bfloat16 or float32."""
+    if not native_bf16:
+      grads_flat = _promoted(grads_flat)
+    # strided views (a `.t()` of a square buffer, an expanded tensor) are copied: the kernels address a
+    # gradient block as base pointer + planned offsets of a contiguous tensor
+    grads_flat = [g if g.is_contiguous() else g.contiguous() for g in grads_flat]
+    param_dtypes = set(p.dtype for p in params_flat)
+    if not (param_dtypes == {torch.float32} or
+            (native_bf16 and param_dtypes == {torch.bfloat16})):
+      params_flat = _promoted(params_flat)
+    return grads_flat, params_flat
+
   # ---------------------------------------------------------------------------
   def update_fn(grads, state, params):
     """DS:3627-3659."""
@@ -1036,21 +1067,19 @@ def distributed_shampoo(
     stats_flat = treedef.flatten_up_to(state.stats)
     grads_flat = treedef.flatten_up_to(grads)
     step = int(state.count)
-    # Mixed-precision training hands over bf16 / fp16 gradients: the reference promotes
-    # them inside its float32 arithmetic; the kernels here take float32 only, so promote
-    # at the door and hand the updates back in the gradient's dtype.
+    # Mixed-precision training hands over bf16 / fp16 gradients: the reference promotes them
+    # inside its float32 arithmetic.  A tree of contiguous bfloat16 gradients on the tree-plan
+    # path is read by the every-step kernels where it lies (a bf16 -> float32 widening is exact:
+    # same values as the promoted copy) and its updates are written in bfloat16; everything else
+    # (fp16, mixed dtypes, strided gradients, the per-block path, a backend without the capability)
+    # is promoted at the door and the updates are handed back in the gradient's dtype.
     grad_dtypes = [g.dtype for g in grads_flat]
-    if donate_state and all(dt == torch.float32 for dt in grad_dtypes):
+    native_bf16 = _native_bf16(grads_flat, params_flat)
+    if donate_state and (native_bf16 or all(dt == torch.float32 for dt in grad_dtypes)):
       upd = _donated_update(grads_flat, stats_flat, params_flat, step)
       if upd is not None:   # state updated in place: the same objects go back
         return (treedef.unflatten(upd), ShampooState(count=state.count + 1, stats=state.stats))
-    grads_flat = [g if g.dtype == torch.float32 else g.to(torch.float32) for g in grads_flat]
-    # strided views (a `.t()` of a square buffer, an expanded tensor) are copied: the kernels address a
-    # gradient block as base pointer + planned offsets of a contiguous tensor
-    grads_flat = [g if g.is_contiguous() else g.contiguous() for g in grads_flat]
-    if any(p.dtype != torch.float32 for p in params_flat):
-      params_flat = [p if p.dtype == torch.float32 else p.to(torch.float32)
-                     for p in params_flat]
+    grads_flat, params_flat = _at_the_door(grads_flat, params_flat, native_bf16)
 
     new_stats = _compute_stats_all(grads_flat, stats_flat, params_flat, step)
     new_stats = _compute_preconditioners(new_stats, params_flat, step)
@@ -1212,12 +1241,8 @@ def distributed_shampoo(
     params_flat, treedef = pytree.tree_flatten(params)
     grads_flat = treedef.flatten_up_to(grads)
     grad_dtypes = [g.dtype for g in grads_flat]
-    grads_flat = [g if g.dtype == torch.float32 else g.to(torch.float32) for g in grads_flat]
-    # strided views (a `.t()` of a square buffer, an expanded tensor) are copied: the kernels address a
-    # gradient block as base pointer + planned offsets of a contiguous tensor
-    grads_flat = [g if g.is_contiguous() else g.contiguous() for g in grads_flat]
-    if any(p.dtype != torch.float32 for p in params_flat):
-      params_flat = [p if p.dtype == torch.float32 else p.to(torch.float32) for p in params_flat]
+    grads_flat, params_flat = _at_the_door(grads_flat, params_flat,
+                                           _native_bf16(grads_flat, params_flat))
     step = int(state.count)
     gstats = state.stats.global_stats
     local_flat = treedef.flatten_up_to(state.stats.local_stats)

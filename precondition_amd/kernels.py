@@ -1069,11 +1069,21 @@ _TDESC_DT = np.dtype([(n, "u8") for n in ("grad", "pgrad", "param", "diag_in", "
                                           "upd_out")] + [("numel", "i8")], align=True)
 
 
+# Capability flag read by distributed_shampoo.update_fn: this backend's every-step calls (the tree
+# plan's Gram update and application, transform_grads_fused) read a uniformly bfloat16 gradient
+# tree where it lies and return bfloat16 updates; a backend without the attribute is handed
+# float32 copies as before.
+NATIVE_BF16_GRADIENTS = True
+_DTYPE_CODE = {torch.float32: 0, torch.bfloat16: 1}   # PS_DTYPE_*
+
+
 @_device_guarded
 def transform_grads_fused(items, cfg: dict):
-  """items: list of dicts with contiguous float32 device tensors
+  """items: list of dicts with contiguous device tensors
   {grad, pgrad|None, param|None, diag_in|None, mom_in, dmom_in}; returns per item
   (update, new_diag|None, new_mom, new_dmom).  cfg: fields of ps_transform_config.
+  `grad` (and with it the update) is float32 or bfloat16, one dtype for the whole list; so is
+  `param`, independently; everything else is float32 in and out.
   The descriptor table is filled column-wise with NumPy."""
   if not items:
     return []
@@ -1083,8 +1093,9 @@ def transform_grads_fused(items, cfg: dict):
   tbl = np.zeros(n, _TDESC_DT)
   keep = []
 
-  def column(name, required=False):
+  def column(name, required=False, typed=False):
     ptrs = np.zeros(n, np.uint64)
+    dtype = None
     col = []
     for i, it in enumerate(items):
       t = it.get(name)
@@ -1095,22 +1106,29 @@ def transform_grads_fused(items, cfg: dict):
         continue
       if not t.is_contiguous():
         t = t.contiguous()
-      if not t.is_cuda or t.dtype != torch.float32:
+      if dtype is None:
+        dtype = t.dtype if typed and t.dtype in _DTYPE_CODE else torch.float32
+      if not t.is_cuda or t.dtype != dtype:
         _require_gpu(t, "_transform_grad")
+        raise ValueError(f"_transform_grad: {name} of item {i} is {t.dtype}, expected {dtype}" +
+                         (" (one dtype, float32 or bfloat16, for the whole list)" if typed else ""))
       col.append(t)
       ptrs[i] = t.data_ptr()
     keep.append(col)
-    return ptrs, col
+    return ptrs, col, _DTYPE_CODE[dtype or torch.float32]
 
-  tbl["grad"], grads = column("grad", required=True)
+  tbl["grad"], grads, grad_code = column("grad", required=True, typed=True)
   _same_device(grads, "_transform_grad")
-  for name in ("pgrad", "param", "diag_in", "mom_in", "dmom_in"):
-    tbl[name], _ = column(name)
+  tbl["param"], _, param_code = column("param", typed=True)
+  for name in ("pgrad", "diag_in", "mom_in", "dmom_in"):
+    tbl[name], _, _ = column(name)
   has_diag = [it.get("diag_in") is not None for it in items]
-  upd = [torch.empty_like(g) for g in grads]
-  mom = [torch.empty_like(g) for g in grads]
-  dmom = [torch.empty_like(g) for g in grads]
-  nd = [torch.empty_like(g) if h else None for g, h in zip(grads, has_diag)]
+  upd = [torch.empty_like(g) for g in grads]      # the gradient's dtype
+  # state is float32 whatever the gradient's dtype (empty_like(g) would follow a bfloat16 gradient)
+  f32_like = lambda g: torch.empty(g.shape, dtype=torch.float32, device=g.device)
+  mom = [f32_like(g) for g in grads]
+  dmom = [f32_like(g) for g in grads]
+  nd = [f32_like(g) if h else None for g, h in zip(grads, has_diag)]
   tbl["upd_out"] = [t.data_ptr() for t in upd]
   tbl["mom_out"] = [t.data_ptr() for t in mom]
   tbl["dmom_out"] = [t.data_ptr() for t in dmom]
@@ -1122,8 +1140,9 @@ def transform_grads_fused(items, cfg: dict):
   descs = C.cast(tbl.ctypes.data, C.POINTER(TransformDesc))
   L = lib()
   ws = _workspace(L.ps_transform_grads_workspace_bytes(descs, n), dev)
-  rc = L.ps_transform_grads_f32(_stream(), descs, n, C.byref(c), ws.data_ptr(), ws.numel())
-  check(rc, "ps_transform_grads_f32")
+  rc = L.ps_transform_grads_typed(_stream(), descs, n, C.byref(c), grad_code, param_code,
+                                  ws.data_ptr(), ws.numel())
+  check(rc, "ps_transform_grads_typed")
   del keep
   return list(zip(upd, nd, mom, dmom))
 

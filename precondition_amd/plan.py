@@ -25,6 +25,20 @@ from . import kernels
 from ._lib import GemmDesc, StatsDesc, check, lib
 
 
+# storage type codes of the ps_*_typed entry points (include/ps_api.h PS_DTYPE_*)
+DTYPE_CODE = {torch.float32: 0, torch.bfloat16: 1}
+
+
+def uniform_dtype(tensors):
+  """The common dtype of `tensors` when it is one the typed kernels read (float32 / bfloat16), else None."""
+  if not tensors:
+    return None
+  dt = tensors[0].dtype
+  if dt not in DTYPE_CODE or any(t.dtype != dt for t in tensors):
+    return None
+  return dt
+
+
 class TreePlan:
 
   def __init__(self):
@@ -73,13 +87,15 @@ class TreePlan:
       row_ld = int(tshape[1]) if nd == 2 else 1
       k = 0
       for blk in pc._partitioner.partition(meta):
-        off = int(blk.storage_offset()) * 4
+        # offset of the block inside its parameter in ELEMENTS: the gradient columns scale it by the
+        # gradient's item size (grad_columns), the float32 result / intermediate columns by 4
+        off = int(blk.storage_offset())
         if nd == 1:
           d = int(blk.shape[0])
           # gram_desc: [d] -> layout 1, k = 1, ld = d
           st_rows.append((i, off, 1, d, 1, d))
           # g^T P as a one-row product: a = [d, 1] (transa), c = [1, d] inside the result
-          a_rows.append((i, off, stat_base + k, d * 0 + 1, d, d, 1, d, d, True, off))
+          a_rows.append((i, off, stat_base + k, d * 0 + 1, d, d, 1, d, d, True, off * 4))
           k += 1
         else:
           m, n = int(blk.shape[0]), int(blk.shape[1])
@@ -89,11 +105,11 @@ class TreePlan:
           st_rows.append((i, off, 1, n, m, row_ld))   # axis 1: layout 1, d = n, k = m
           # stage A: X [n, m] = g^T P_L (transa);  stage B: Y [m, n] = X^T P_R into the result
           a_rows.append((i, off, stat_base + k, n, m, m, row_ld, m, m, False, x_off * 4))
-          b_rows.append((i, stat_base + k + 1, x_off * 4, off, m, n, n, m, n, row_ld))
+          b_rows.append((i, stat_base + k + 1, x_off * 4, off * 4, m, n, n, m, n, row_ld))
           # symmetric preconditioners (apply_preconditioners): X^T [m, n] = P_L g, Y = X^T P_R
           # (param, goff, stat, m, n, k, lda, ldb, ldc, xoff) / (param, stat, xoff, coff, m, n, k, lda, ldb, ldc)
           sa_rows.append((i, off, stat_base + k, m, n, m, m, row_ld, n, x_off * 4))
-          sb_rows.append((i, stat_base + k + 1, x_off * 4, off, m, n, n, n, n, row_ld))
+          sb_rows.append((i, stat_base + k + 1, x_off * 4, off * 4, m, n, n, n, n, row_ld))
           x_off += m * n
           k += 2
       pl.n_stats_of.append(k)
@@ -176,14 +192,39 @@ class TreePlan:
   def _ptrs(tensors) -> np.ndarray:
     return np.fromiter((t.data_ptr() for t in tensors), np.uint64, len(tensors))
 
-  def check_dense(self, tensors, what: str):
-    """Contiguous float32 tensors on one device (the plan addresses them by pointer)."""
+  def check_dense(self, tensors, what: str, gradients: bool = False):
+    """Contiguous float32 tensors on one device (the plan addresses them by pointer).  gradients:
+    a list that is uniformly float32 OR uniformly bfloat16 (read natively by the typed kernels)."""
     dev = tensors[0].device
+    dt = tensors[0].dtype if gradients and tensors[0].dtype in DTYPE_CODE else torch.float32
     for t in tensors:
-      if t.dtype != torch.float32 or not t.is_cuda or t.device != dev or not t.is_contiguous():
+      if t.dtype != dt or not t.is_cuda or t.device != dev or not t.is_contiguous():
         kernels._require_gpu(t, what)
-        raise ValueError(f"{what}: the tree plan needs contiguous float32 tensors on one device")
+        raise ValueError(f"{what}: the tree plan needs contiguous float32 tensors (gradients: all "
+                         "float32 or all bfloat16) on one device")
     return dev
+
+  def grad_columns(self, gp: np.ndarray, itemsize: int) -> dict:
+    """The pointer columns that address GRADIENT blocks, from the base address of every parameter's
+    gradient (gp, uint64) and the gradient's item size: base + element offset * itemsize.
+      st_g: `g` of the statistics table;  a_a: `a` of stage A in the reference orientation (the
+      one-row products of 1-D blocks included);  sa_b: `b` of stage A in the symmetric orientation.
+    Every other offset column (a_coff, b_xoff, b_coff, sa_xoff) addresses float32 buffers."""
+    sz = np.uint64(itemsize)
+    none = np.zeros(0, np.uint64)
+    return dict(
+        st_g=gp[self.st_param] + self.st_goff * sz if len(self.stats_tbl) else none,
+        a_a=gp[self.a_param] + self.a_goff * sz if len(self.a_tbl) else none,
+        sa_b=gp[self.sa_param] + self.sa_goff * sz if len(getattr(self, "sa_tbl", ())) else none)
+
+  def symmetric_layout(self, symmetric_precs: bool, grad_dtype) -> bool:
+    """Does stage A run in the symmetric orientation X^T = P_L g?  One grouped call carries one
+    storage type per operand, and the one-row products of 1-D blocks keep the gradient as operand A:
+    a bfloat16 tree that has such blocks runs the reference orientation (bit-identical results, see
+    build), so that the call -- and with it the library's split-K choice -- stays the float32 one."""
+    if not (symmetric_precs and len(getattr(self, "sa_tbl", ())) > 0):
+      return False
+    return grad_dtype == torch.float32 or len(self.a_vec_rows) == 0
 
   def stats_update(self, grads_flat, stats_in, stats_out, w1: float, w2: float):
     """gram_weighted_update of every (block, axis) of the tree (DS:1582-1590) in one launch.
@@ -191,21 +232,22 @@ class TreePlan:
     S = len(self.stats_tbl)
     if S == 0:
       return
-    dev = self.check_dense(grads_flat, "gram_weighted_update")
+    dev = self.check_dense(grads_flat, "gram_weighted_update", gradients=True)
+    gdt = grads_flat[0].dtype
     if self.check_dense(list(stats_in) + list(stats_out), "gram_weighted_update") != dev:
       raise ValueError("gram_weighted_update: gradients and statistics live on different devices")
     tbl = self.stats_tbl.copy()
     gp = self._ptrs(grads_flat)
-    tbl["g"] = gp[self.st_param] + self.st_goff
+    tbl["g"] = self.grad_columns(gp, grads_flat[0].element_size())["st_g"]
     tbl["stat_in"] = self._ptrs(stats_in)
     tbl["stat_out"] = self._ptrs(stats_out)
     with torch.cuda.device(dev):
       descs = C.cast(tbl.ctypes.data, C.POINTER(StatsDesc))
       L = lib()
       ws = kernels._workspace(L.ps_stats_update_grouped_workspace_bytes(descs, S), dev)
-      rc = L.ps_stats_update_grouped_f32(kernels._stream(), descs, S, float(w1), float(w2),
-                                         ws.data_ptr(), ws.numel())
-    check(rc, "ps_stats_update_grouped_f32")
+      rc = L.ps_stats_update_grouped_typed(kernels._stream(), descs, S, DTYPE_CODE[gdt], float(w1),
+                                           float(w2), ws.data_ptr(), ws.numel())
+    check(rc, "ps_stats_update_grouped_typed")
 
   def apply_preconditioners(self, grads_flat, precs_flat, results, symmetric_precs=False):
     """Preconditioner.preconditioned_grad (DS:1645-1708) for every planned parameter:
@@ -215,25 +257,28 @@ class TreePlan:
     are issued as X^T = P_L g, Y = X^T P_R (bit-identical, faster operand layout; see build)."""
     if len(self.a_tbl) == 0:
       return
-    dev = self.check_dense(grads_flat, "preconditioned_grad")
+    dev = self.check_dense(grads_flat, "preconditioned_grad", gradients=True)
+    gdt = grads_flat[0].dtype
+    gcols = self.grad_columns(self._ptrs(grads_flat), grads_flat[0].element_size())
     self.check_dense([p for p in precs_flat] + [r for r in results if r is not None],
                      "preconditioned_grad")
     x = torch.empty(max(self.x_elems, 1), dtype=torch.float32, device=dev)
     xp = np.uint64(x.data_ptr())
-    gp = self._ptrs(grads_flat)
     pp = self._ptrs(precs_flat)
     rp = np.fromiter((0 if r is None else r.data_ptr() for r in results), np.uint64,
                      len(results))
     ta = self.a_tbl.copy()
-    ta["a"] = gp[self.a_param] + self.a_goff
+    ta["a"] = gcols["a_a"]
     ta["b"] = pp[self.a_stat]
     ta["c"] = np.where(self.a_c_is_res, rp[self.a_param], xp) + self.a_coff
-    sym = symmetric_precs and len(getattr(self, "sa_tbl", ())) > 0
+    sym = self.symmetric_layout(symmetric_precs, gdt)
+    # storage of stage A's operands: the gradient is A in the reference orientation, B in the symmetric one
+    a_dt, b_dt = (0, DTYPE_CODE[gdt]) if sym else (DTYPE_CODE[gdt], 0)
     if sym:
       vec = ta[self.a_vec_rows]
       sa = self.sa_tbl.copy()
       sa["a"] = pp[self.sa_stat]
-      sa["b"] = gp[self.sa_param] + self.sa_goff
+      sa["b"] = gcols["sa_b"]
       sa["c"] = xp + self.sa_xoff
       ta = np.concatenate([sa, vec]) if len(vec) else sa
     L = lib()
@@ -252,8 +297,9 @@ class TreePlan:
         n = len(tbl)
         descs = C.cast(tbl.ctypes.data, C.POINTER(GemmDesc))
         ws = kernels._workspace(L.ps_gemm_grouped_workspace_bytes(descs, n), dev)
-        rc = L.ps_gemm_grouped_f32(kernels._stream(), descs, n, ws.data_ptr(), ws.numel())
-        check(rc, "ps_gemm_grouped_f32")
+        rc = L.ps_gemm_grouped_typed(kernels._stream(), descs, n, a_dt, b_dt, ws.data_ptr(), ws.numel())
+        check(rc, "ps_gemm_grouped_typed")
+        a_dt = b_dt = 0   # stage B reads the float32 intermediate
     del x  # the caching allocator keeps it alive until the stream has consumed it
 
 
@@ -288,7 +334,8 @@ class DonatedStep:
 
   def bind(self, stats_flat, grads_flat, params_flat, symmetric_precs: bool):
     pl = self.plan
-    dev = pl.check_dense(grads_flat, "update (donated state)")
+    dev = pl.check_dense(grads_flat, "update (donated state)", gradients=True)
+    self.gdtype = grads_flat[0].dtype
     stats = [s for st in stats_flat for s in st.statistics]
     precs = [p for st in stats_flat for p in st.preconditioners]
     moms = [st.momentum.quantized for st in stats_flat]
@@ -300,9 +347,12 @@ class DonatedStep:
     n = pl.n_params
     self.dev = dev
     # buffers owned by the step (valid until the next update call)
-    if getattr(self, "upd", None) is None:
-      self.upd = [torch.empty_like(g) for g in grads_flat]
-      self.pg = [None if sk else torch.empty_like(g) for g, sk in zip(grads_flat, pl.skipped)]
+    if getattr(self, "upd", None) is None or self.upd[0].dtype != self.gdtype:
+      self.upd = [torch.empty_like(g) for g in grads_flat]       # the gradient's dtype
+    if getattr(self, "pg", None) is None:
+      # float32 whatever the gradient's dtype (empty_like(g) would make them bfloat16)
+      self.pg = [None if sk else torch.empty(g.shape, dtype=torch.float32, device=dev)
+                 for g, sk in zip(grads_flat, pl.skipped)]
       self.x = torch.empty(max(pl.x_elems, 1), dtype=torch.float32, device=dev)
     sp, prp = pl._ptrs(stats), pl._ptrs(precs)
     rp = np.fromiter((0 if r is None else r.data_ptr() for r in self.pg), np.uint64, n)
@@ -316,7 +366,9 @@ class DonatedStep:
     ta = pl.a_tbl.copy()
     ta["b"] = prp[pl.a_stat] if len(ta) else prp[:0]
     ta["c"] = (np.where(pl.a_c_is_res, rp[pl.a_param], xp) + pl.a_coff) if len(ta) else prp[:0]
-    self.sym = bool(symmetric_precs and len(getattr(pl, "sa_tbl", ())) > 0)
+    self.sym = pl.symmetric_layout(symmetric_precs, self.gdtype)
+    gcode = DTYPE_CODE[self.gdtype]
+    self.a_dtypes = (0, gcode) if self.sym else (gcode, 0)
     if self.sym:
       vec = ta[pl.a_vec_rows]
       sa = pl.sa_tbl.copy()
@@ -366,17 +418,21 @@ class DonatedStep:
 
   def qualifies(self, grads_flat, params_flat) -> bool:
     """Checked on EVERY step, before the pointer comparison: the raw-pointer tables read a gradient as a
-    contiguous float32 tensor of the bound shape.  A tensor with the same data_ptr and shape but other
-    strides (a `.t()` view of a square weight, an expanded tensor) or another dtype must not reach them;
-    such a step takes the functional path (which copies / converts), it does not raise."""
+    contiguous tensor of the bound shape and dtype (float32 or bfloat16, one for the whole tree).  A
+    tensor with the same data_ptr and shape but other strides (a `.t()` view of a square weight, an
+    expanded tensor) or another dtype must not reach them; such a step takes the functional path (which
+    copies / converts), it does not raise.  Parameters (read with weight decay only) are uniformly
+    float32 or uniformly bfloat16, independently of the gradients."""
     for g, u in zip(grads_flat, self.upd):
-      if (g.dtype != torch.float32 or not g.is_contiguous() or g.device != self.dev or
+      if (g.dtype != self.gdtype or not g.is_contiguous() or g.device != self.dev or
           g.shape != u.shape):
         return False
     if self.use_params:
+      pdt = uniform_dtype(params_flat)
+      if pdt is None:
+        return False
       for p_, u in zip(params_flat, self.upd):
-        if (p_.dtype != torch.float32 or not p_.is_contiguous() or p_.device != self.dev or
-            p_.shape != u.shape):
+        if not p_.is_contiguous() or p_.device != self.dev or p_.shape != u.shape:
           return False
     return True
 
@@ -386,21 +442,23 @@ class DonatedStep:
     if self.gp is not None and np.array_equal(gp, self.gp):
       return
     self.gp = gp
+    cols = pl.grad_columns(gp, self.upd[0].element_size())
     if len(self.st_tbl):
-      self.st_tbl["g"] = gp[pl.st_param] + pl.st_goff
+      self.st_tbl["g"] = cols["st_g"]
     if self.sym:
-      self.ta["b"][:self.n_sa] = gp[pl.sa_param] + pl.sa_goff
-      if len(self.ta) > self.n_sa:
-        vr = pl.a_vec_rows
-        self.ta["a"][self.n_sa:] = gp[pl.a_param[vr]] + pl.a_goff[vr]
+      self.ta["b"][:self.n_sa] = cols["sa_b"]
+      if len(self.ta) > self.n_sa:     # (float32 gradients only: symmetric_layout)
+        self.ta["a"][self.n_sa:] = cols["a_a"][pl.a_vec_rows]
     elif len(self.ta):
-      self.ta["a"] = gp[pl.a_param] + pl.a_goff
+      self.ta["a"] = cols["a_a"]
     self.tt["grad"] = gp
 
   def step(self, grads_flat, params_flat, cfg, do_stats: bool, w1: float, w2: float):
     """Enqueues the step; returns the update tensors (owned by this object)."""
     self._patch_grads(grads_flat)    # (the caller checked qualifies() for this step)
+    gcode, pcode = DTYPE_CODE[self.gdtype], 0
     if self.use_params:
+      pcode = DTYPE_CODE[params_flat[0].dtype]
       pp = self.plan._ptrs(params_flat)
       if self.pp_params is None or not np.array_equal(pp, self.pp_params):
         self.pp_params = pp
@@ -409,19 +467,20 @@ class DonatedStep:
     stream = kernels._stream()
     with torch.cuda.device(self.dev):
       if do_stats and len(self.st_tbl):
-        rc = L.ps_stats_update_grouped_f32(stream, C.cast(self.st_tbl.ctypes.data, C.POINTER(StatsDesc)),
-                                           len(self.st_tbl), float(w1), float(w2),
-                                           self.ws_stats.data_ptr(), self.ws_stats.numel())
-        check(rc, "ps_stats_update_grouped_f32")
-      for tbl, ws in ((self.ta, self.ws_a), (self.tb, self.ws_b)):
+        rc = L.ps_stats_update_grouped_typed(stream, C.cast(self.st_tbl.ctypes.data, C.POINTER(StatsDesc)),
+                                             len(self.st_tbl), gcode, float(w1), float(w2),
+                                             self.ws_stats.data_ptr(), self.ws_stats.numel())
+        check(rc, "ps_stats_update_grouped_typed")
+      for tbl, ws, (a_dt, b_dt) in ((self.ta, self.ws_a, self.a_dtypes), (self.tb, self.ws_b, (0, 0))):
         if len(tbl):
-          rc = L.ps_gemm_grouped_f32(stream, C.cast(tbl.ctypes.data, C.POINTER(GemmDesc)), len(tbl),
-                                     ws.data_ptr(), ws.numel())
-          check(rc, "ps_gemm_grouped_f32")
+          rc = L.ps_gemm_grouped_typed(stream, C.cast(tbl.ctypes.data, C.POINTER(GemmDesc)), len(tbl),
+                                       a_dt, b_dt, ws.data_ptr(), ws.numel())
+          check(rc, "ps_gemm_grouped_typed")
       c = kernels.TransformConfig()
       for k, v in cfg.items():
         setattr(c, k, v)
-      rc = L.ps_transform_grads_f32(stream, C.cast(self.tt.ctypes.data, C.POINTER(kernels.TransformDesc)),
-                                    self.plan.n_params, C.byref(c), self.ws_t.data_ptr(), self.ws_t.numel())
-      check(rc, "ps_transform_grads_f32")
+      rc = L.ps_transform_grads_typed(stream, C.cast(self.tt.ctypes.data, C.POINTER(kernels.TransformDesc)),
+                                      self.plan.n_params, C.byref(c), gcode, pcode,
+                                      self.ws_t.data_ptr(), self.ws_t.numel())
+      check(rc, "ps_transform_grads_typed")
     return self.upd

@@ -1,7 +1,10 @@
 """Every-step cost of update_fn on the ViT-B tree (dev only)."""
 import os; os.environ.setdefault("PS_DEV_ENV", "1")   # developer switches (PS_*) are read only under PS_DEV_ENV=1
 import os, sys, time
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if "--package-root" in sys.argv:   # import precondition_amd (and bench) from another checkout, e.g. a build of the parent commit
+  ROOT = os.path.abspath(sys.argv[sys.argv.index("--package-root") + 1])
+sys.path.insert(0, ROOT)
 import numpy as np, torch
 import precondition_amd as pa
 import bench
@@ -9,6 +12,9 @@ dev = torch.device("cuda:0")
 rng = np.random.default_rng(0)
 params = [torch.from_numpy((rng.standard_normal(s) * 0.02).astype(np.float32)).to(dev) for s in bench.VIT_B_SHAPES]
 grads = [torch.from_numpy((rng.standard_normal(s) * 0.02).astype(np.float32)).to(dev) for s in bench.VIT_B_SHAPES]
+if "--bf16" in sys.argv:   # gradients and parameters handed over in bfloat16 (pure-bf16 model)
+  params = [p.to(torch.bfloat16) for p in params]
+  grads = [g.to(torch.bfloat16) for g in grads]
 kw = {}
 if "--quant" in sys.argv:  # int8 momentum + int16 statistics / preconditioners (needs a batch axis)
   import tempfile

@@ -223,7 +223,7 @@ template <> struct GramTiles<2> { static constexpr int N = 2; static constexpr i
 template <> struct GramTiles<3> { static constexpr int N = 2; static constexpr int TI[3] = {2, 3, 0}, TJ[3] = {3, 3, 0}; };
 
 template <int W>
-__device__ __forceinline__ void cj_gram_body(const float* G, int ld, const int (&goff)[2],
+__device__ __forceinline__ void cj_gram_tiles(const float* G, int ld, const int (&goff)[2],
                                              const int (&soff)[2], float* smem, float* P,
                                              int lane) {
   using T = GramTiles<W>;
@@ -301,10 +301,10 @@ __global__ __launch_bounds__(256, 2) void cj_gram_kernel(EighBlock* blocks, cons
   }
   float* P = eb->V + (int64_t)te.k * JP * JP;
   switch (wave) {
-    case 0: cj_gram_body<0>(G, ld, goff, soff, smem, P, lane); break;
-    case 1: cj_gram_body<1>(G, ld, goff, soff, smem, P, lane); break;
-    case 2: cj_gram_body<2>(G, ld, goff, soff, smem, P, lane); break;
-    default: cj_gram_body<3>(G, ld, goff, soff, smem, P, lane); break;
+    case 0: cj_gram_tiles<0>(G, ld, goff, soff, smem, P, lane); break;
+    case 1: cj_gram_tiles<1>(G, ld, goff, soff, smem, P, lane); break;
+    case 2: cj_gram_tiles<2>(G, ld, goff, soff, smem, P, lane); break;
+    default: cj_gram_tiles<3>(G, ld, goff, soff, smem, P, lane); break;
   }
 }
 

@@ -18,17 +18,27 @@
 // k = 8c+4h+s at MFMA step s) identically for A and B, which only changes the
 // summation order of the exact-f32 chain.
 //
+// An operand may be stored as bfloat16 (OperandH).  A bf16 -> float32 widening is exact, so a
+// product that reads an operand as bf16 and widens it on the way into LDS returns the bits of the
+// float32 kernel on the promoted copy -- as long as the LDS image and the k order are the float32
+// kernel's.  They are: the tile loader is chosen per operand by its storage type and there is ONE
+// set of K loops (gemm_tile_accum, deep_issue_first + deep_run) and one compute_ktile behind
+// every loader pair, so a product may mix one bf16 and one float32 operand.
+//
 // Replaces the XLA dot at DS:671,674,845,846 (Newton products) and DS:1469
 // (statistics Gram matrix) of the reference.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace psk {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int TILE = 128;      // BM = BN
 constexpr int NTHREADS = 256;  // 4 wavefronts
@@ -51,6 +61,36 @@ __device__ inline void gstore1(float* p, float v) { *(float PS_GLOBAL*)(p) = v; 
 __device__ inline void gstore1_wt(float* p, float v) {
   __hip_atomic_store((float PS_GLOBAL*)(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+
+// bf16 bits -> float32: the value's upper 16 bits
+__device__ __forceinline__ float widen_lo(uint32_t w) { return __uint_as_float(w << 16); }
+__device__ __forceinline__ float widen_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
+__device__ __forceinline__ float gload1h(const uint16_t* p) {
+  return __uint_as_float((uint32_t)(*(const uint16_t PS_GLOBAL*)(p)) << 16);
+}
+// 4 consecutive bf16 (8-byte aligned) -> f32x4
+__device__ __forceinline__ f32x4 widen4(u32x2 r) {
+  f32x4 v = {widen_lo(r[0]), widen_hi(r[0]), widen_lo(r[1]), widen_hi(r[1])};
+  return v;
+}
+__device__ __forceinline__ u32x2 gload4h_raw(const uint16_t* p) { return *(const u32x2 PS_GLOBAL*)(p); }
+
+// Storage type of an array that a kernel reads as float32: float, or the bits of a bf16 (H).
+template <bool H>
+using storage_t = typename std::conditional<H, uint16_t, float>::type;
+// Element i (four elements from i) as float32 of an array that descriptor tables carry as
+// `const float*` whatever its storage; H: it holds bf16, i counts 2-byte elements.
+template <bool H>
+__device__ __forceinline__ float gload1t(const float* p, int64_t i) {
+  if constexpr (H) return gload1h((const uint16_t*)p + i);
+  else return gload1(p + i);
+}
+template <bool H>
+__device__ __forceinline__ f32x4 gload4t(const float* p, int64_t i) {
+  if constexpr (H) return widen4(gload4h_raw((const uint16_t*)p + i));
+  else return gload4(p + i);
+}
+
 template <bool WT>
 __device__ inline void tstore1(float* p, float v) {
   if (WT) gstore1_wt(p, v); else gstore1(p, v);
@@ -70,18 +110,29 @@ struct SmemCfg {
   static constexpr int total(int la, int lb) { return 2 * (op_size(la) + op_size(lb)); }
 };
 
-struct Operand {
-  const float* p;
-  int ld;
+// T: storage of the elements, float or uint16_t (bf16 bits)
+template <class T>
+struct OperandT {
+  const T* p;
+  int ld;    // in elements
   int mn0;   // first row (A) / column (B) of this tile
   int MN;    // logical extent along mn (guarded loads only)
   int K;     // logical extent along k  (guarded loads only)
-  bool vec;  // 16-byte vector loads are legal (base and ld aligned)
+  bool vec;  // vector loads of four elements are legal (base and ld aligned: 16 bytes / 8 bytes)
 };
+using Operand = OperandT<float>;
+using OperandH = OperandT<uint16_t>;
 
 // ---- global -> registers ---------------------------------------------------
+// One loader per storage type behind one interface: Reg (a thread's prefetch register for four
+// elements), Op, NV, load (global -> Reg), store (Reg -> the float32 LDS image).
+template <int LAYOUT, int BK, bool GUARD, class T = float>
+struct TileLoader;
+
 template <int LAYOUT, int BK, bool GUARD>
-struct TileLoader {
+struct TileLoader<LAYOUT, BK, GUARD, float> {
+  using Reg = f32x4;
+  using Op = Operand;
   static constexpr int NV = (TILE * BK / 4) / NTHREADS;  // float4 per thread
   static_assert(NV >= 1, "BK too small");
 
@@ -179,6 +230,73 @@ struct TileLoader {
       float* dst = (LAYOUT == KC) ? s + mn * SmemCfg<BK>::KC_LD + k
                                   : s + k * SmemCfg<BK>::MC_LD + mn;
       *reinterpret_cast<f32x4*>(dst) = r[v];
+    }
+  }
+};
+
+// bf16 storage: fetches the elements of the float32 loader's f32x4 slots (same thread -> element
+// map: 4 bf16 = one 8-byte load per slot), keeps the RAW halves in the prefetch registers (half
+// the registers of a float32 set) and widens when it writes the same [128][BK+4] / [BK][128+4]
+// image.
+template <int LAYOUT, int BK, bool GUARD>
+struct TileLoader<LAYOUT, BK, GUARD, uint16_t> {
+  using Reg = u32x2;
+  using Op = OperandH;
+  using F = TileLoader<LAYOUT, BK, GUARD>;   // thread -> element map of the float32 loader
+  static constexpr int NV = F::NV;
+  static constexpr int ROWS_PER_V = F::ROWS_PER_V;
+
+  __device__ static inline void load(const OperandH& op, int k0, int tid, u32x2 (&r)[NV]) {
+    if (!GUARD) {
+      // wave-uniform base + one 32-bit byte offset per lane, as the float32 load (2-byte elements)
+      uint32_t off = F::lane_byte_offset(op.ld, tid) >> 1;
+      asm volatile("" : "+v"(off));
+      const uint16_t* base = LAYOUT == KC ? op.p + (int64_t)op.mn0 * op.ld + k0
+                                          : op.p + (int64_t)k0 * op.ld + op.mn0;
+#pragma unroll
+      for (int v = 0; v < NV; ++v)
+        r[v] = *(const u32x2 PS_GLOBAL*)((const char PS_GLOBAL*)(base + (int64_t)(v * ROWS_PER_V) * op.ld) +
+                                         (uint64_t)off);
+      return;
+    }
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      int mn, k;
+      F::coords(v, tid, mn, k);
+      const int gmn = op.mn0 + mn;
+      const int gk = k0 + k;
+      // run of 4 elements along the contiguous direction: k (KC) or mn (MC)
+      const uint16_t* src = LAYOUT == KC ? op.p + (int64_t)gmn * op.ld + gk
+                                         : op.p + (int64_t)gk * op.ld + gmn;
+      const bool row_ok = LAYOUT == KC ? gmn < op.MN : gk < op.K;
+      const int first = LAYOUT == KC ? gk : gmn;
+      const int extent = LAYOUT == KC ? op.K : op.MN;
+      u32x2 t = {0u, 0u};
+      if (row_ok) {
+        if (op.vec && first + 3 < extent) {
+          t = gload4h_raw(src);
+        } else {
+          uint32_t h[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (first + e < extent) h[e] = *(const uint16_t PS_GLOBAL*)(src + e);
+          t[0] = h[0] | (h[1] << 16);
+          t[1] = h[2] | (h[3] << 16);
+        }
+      }
+      r[v] = t;
+    }
+  }
+
+  // registers -> LDS image (widened: the float32 loader's image)
+  __device__ static inline void store(float* s, int tid, const u32x2 (&r)[NV]) {
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      int mn, k;
+      F::coords(v, tid, mn, k);
+      float* dst = (LAYOUT == KC) ? s + mn * SmemCfg<BK>::KC_LD + k
+                                  : s + k * SmemCfg<BK>::MC_LD + mn;
+      *reinterpret_cast<f32x4*>(dst) = widen4(r[v]);
     }
   }
 };
@@ -285,18 +403,23 @@ __device__ __forceinline__ void seg_finish(f32x16 (&acc)[2][2], const f32x16 (&t
 // The two register sets of the DEEP K loop, split in two calls so that a caller that walks a
 // list of tiles can issue the first loads of its NEXT tile before the epilogue of the current
 // one (deep_issue_first), and enter that tile's K loop with them in flight (deep_run).
-template <int LA, int LB, int BK, bool GUARD>
+// TA / TB: storage of A / B (deduced from the operands by the functions below).
+template <int LA, int LB, int BK, bool GUARD, class TA = float, class TB = float>
 struct DeepSets {
-  f32x4 ra0[TileLoader<LA, BK, GUARD>::NV], rb0[TileLoader<LB, BK, GUARD>::NV];
-  f32x4 ra1[TileLoader<LA, BK, GUARD>::NV], rb1[TileLoader<LB, BK, GUARD>::NV];
+  using LdA = TileLoader<LA, BK, GUARD, TA>;
+  using LdB = TileLoader<LB, BK, GUARD, TB>;
+  typename LdA::Reg ra0[LdA::NV];
+  typename LdB::Reg rb0[LdB::NV];
+  typename LdA::Reg ra1[LdA::NV];
+  typename LdB::Reg rb1[LdB::NV];
 };
 
 // Issues the global loads of K-tiles 0 and 1 (set 0 and set 1).
-template <int LA, int LB, int BK, bool GUARD>
-__device__ inline void deep_issue_first(const Operand& A, const Operand& B, int Kext,
-                                        DeepSets<LA, LB, BK, GUARD>& r) {
-  using LdA = TileLoader<LA, BK, GUARD>;
-  using LdB = TileLoader<LB, BK, GUARD>;
+template <int LA, int LB, int BK, bool GUARD, class TA, class TB>
+__device__ inline void deep_issue_first(const OperandT<TA>& A, const OperandT<TB>& B, int Kext,
+                                        DeepSets<LA, LB, BK, GUARD, TA, TB>& r) {
+  using LdA = TileLoader<LA, BK, GUARD, TA>;
+  using LdB = TileLoader<LB, BK, GUARD, TB>;
   const int tid = threadIdx.x;
   const int nk = (Kext + BK - 1) / BK;
   LdA::load(A, 0, tid, r.ra0);
@@ -308,12 +431,12 @@ __device__ inline void deep_issue_first(const Operand& A, const Operand& B, int 
 }
 
 // acc += A * B with K-tiles 0 and 1 already requested by deep_issue_first.  Ends with a barrier.
-template <int LA, int LB, int BK, bool GUARD, bool SEGV = false>
-__device__ inline void deep_run(const Operand& A, const Operand& B, int Kext, float* smem,
-                                f32x16 (&acc)[2][2], DeepSets<LA, LB, BK, GUARD>& r,
+template <int LA, int LB, int BK, bool GUARD, bool SEGV = false, class TA, class TB>
+__device__ inline void deep_run(const OperandT<TA>& A, const OperandT<TB>& B, int Kext, float* smem,
+                                f32x16 (&acc)[2][2], DeepSets<LA, LB, BK, GUARD, TA, TB>& r,
                                 unsigned long long* t_fill = nullptr, bool seg = false) {
-  using LdA = TileLoader<LA, BK, GUARD>;
-  using LdB = TileLoader<LB, BK, GUARD>;
+  using LdA = TileLoader<LA, BK, GUARD, TA>;
+  using LdB = TileLoader<LB, BK, GUARD, TB>;
   constexpr int OPS = SmemCfg<BK>::op_size(LA);
   constexpr int STG = SmemCfg<BK>::op_size(LA) + SmemCfg<BK>::op_size(LB);
   constexpr int SEGT = SEG_K / BK;   // K-tiles per segment (even)
@@ -620,12 +743,19 @@ __device__ inline void deep_run_pipe_seg(const Operand& A, const Operand& B, int
 //   workgroup's K loop cannot go faster than one memory round trip per K-tile even when the
 //   MFMA pipe is free (measured: 6900 cycles per K-tile whether 2 or 3 workgroups shared
 //   the CU).  Same summation order, bit-identical results.
-template <int LA, int LB, int BK, bool GUARD, bool DEEP = false, bool PIPE = false, bool SEGV = false>
-__device__ inline void gemm_tile_accum(const Operand& A, const Operand& B, int Kext,
+// A and B may each be stored as float32 or bf16 (Operand / OperandH); the explicitly scheduled
+// loops (PIPE: deep_run_pipe, deep_run_pipe_seg) read float32 only.
+template <class TA, class TB>
+constexpr bool both_f32 = std::is_same<TA, float>::value && std::is_same<TB, float>::value;
+
+template <int LA, int LB, int BK, bool GUARD, bool DEEP = false, bool PIPE = false, bool SEGV = false,
+          class TA, class TB>
+__device__ inline void gemm_tile_accum(const OperandT<TA>& A, const OperandT<TB>& B, int Kext,
                                        float* smem, f32x16 (&acc)[2][2],
                                        unsigned long long* t_fill = nullptr, bool seg = false) {
-  using LdA = TileLoader<LA, BK, GUARD>;
-  using LdB = TileLoader<LB, BK, GUARD>;
+  static_assert(!PIPE || both_f32<TA, TB>, "deep_run_pipe and deep_run_pipe_seg are float32 only");
+  using LdA = TileLoader<LA, BK, GUARD, TA>;
+  using LdB = TileLoader<LB, BK, GUARD, TB>;
   constexpr int OPS = SmemCfg<BK>::op_size(LA);
   constexpr int STG = SmemCfg<BK>::op_size(LA) + SmemCfg<BK>::op_size(LB);
   const int tid = threadIdx.x;
@@ -636,7 +766,8 @@ __device__ inline void gemm_tile_accum(const Operand& A, const Operand& B, int K
 
   const int nk = (Kext + BK - 1) / BK;
   if (!DEEP) {
-    f32x4 ra[LdA::NV], rb[LdB::NV];
+    typename LdA::Reg ra[LdA::NV];
+    typename LdB::Reg rb[LdB::NV];
     LdA::load(A, 0, tid, ra);
     LdB::load(B, 0, tid, rb);
     LdA::store(smem, tid, ra);
@@ -666,7 +797,7 @@ __device__ inline void gemm_tile_accum(const Operand& A, const Operand& B, int K
     return;
   }
   // ---- two register sets, loop unrolled by two so that the set indices are static ----
-  DeepSets<LA, LB, BK, GUARD> sets;
+  DeepSets<LA, LB, BK, GUARD, TA, TB> sets;
   deep_issue_first<LA, LB, BK, GUARD>(A, B, Kext, sets);
   if constexpr (PIPE && BK == 32 && !GUARD)
     deep_run_pipe<BK, LA, LB>(A, B, Kext, smem, acc, sets, t_fill);
@@ -674,11 +805,13 @@ __device__ inline void gemm_tile_accum(const Operand& A, const Operand& B, int K
     deep_run<LA, LB, BK, GUARD, SEGV>(A, B, Kext, smem, acc, sets, t_fill, seg);
 }
 
-template <int LA, int LB, int BK, bool GUARD, bool DEEP = false, bool PIPE = false, bool SEGV = false>
-__device__ inline void gemm_tile(const Operand& A, const Operand& B, int Kext,
+template <int LA, int LB, int BK, bool GUARD, bool DEEP = false, bool PIPE = false, bool SEGV = false,
+          class TA, class TB>
+__device__ inline void gemm_tile(const OperandT<TA>& A, const OperandT<TB>& B, int Kext,
                                  float* smem, f32x16 (&acc)[2][2],
                                  unsigned long long* t_fill = nullptr, bool seg = false) {
   if constexpr (SEGV && PIPE && DEEP && BK == 32 && !GUARD) {
+    static_assert(both_f32<TA, TB>, "deep_run_pipe_seg is float32 only");
     // two complete loops behind one uniform branch (the caller guarantees Kext % SEG_K == 0)
     if (seg) {
       deep_run_pipe_seg<BK, LA, LB>(A, B, Kext, smem, acc, t_fill);

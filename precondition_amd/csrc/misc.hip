@@ -5,11 +5,9 @@
 #include <vector>
 
 #include <new>
-#include <type_traits>
 
 #include "common.h"
 #include "gemm_core.hip.h"
-#include "gemm_core_widen.hip.h"
 
 using namespace psk;
 
@@ -144,16 +142,6 @@ struct GTile { int task; short tm, tn; int ks; };
 // order) instead of running 128 x 128 MFMA tiles with one useful row.  The ViT-B tree has 149
 // such blocks: ~1000 of the 6300 tiles of an application stage.
 // AH / BH: the operand is stored as bf16 (the pointer addresses 2-byte elements, strides in elements).
-template <bool H>
-__device__ __forceinline__ float gemv_load1(const float* p, int64_t i) {
-  if constexpr (H) return gload1h((const uint16_t*)p + i);
-  else return gload1(p + i);
-}
-template <bool H>
-__device__ __forceinline__ f32x4 gemv_load4(const float* p, int64_t i) {
-  if constexpr (H) return widen4(gload4h_raw((const uint16_t*)p + i));
-  else return gload4(p + i);
-}
 template <bool AH = false, bool BH = false>
 __device__ inline void gemv_row_tile(const float* a, int64_t astride, const float* b, int ldb,
                                      float* c, int n, int k, int col0, bool vecb, float* smem) {
@@ -168,8 +156,8 @@ __device__ inline void gemv_row_tile(const float* a, int64_t astride, const floa
       float av[8];
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
-        v[u] = gemv_load4<BH>(b, (int64_t)(kk + 8 * u) * ldb + col);
-        av[u] = gemv_load1<AH>(a, (int64_t)(kk + 8 * u) * astride);
+        v[u] = gload4t<BH>(b, (int64_t)(kk + 8 * u) * ldb + col);
+        av[u] = gload1t<AH>(a, (int64_t)(kk + 8 * u) * astride);
       }
 #pragma unroll
       for (int u = 0; u < 8; ++u)
@@ -177,17 +165,17 @@ __device__ inline void gemv_row_tile(const float* a, int64_t astride, const floa
         for (int e = 0; e < 4; ++e) s[e] = __fmaf_rn(av[u], v[u][e], s[e]);
     }
     for (; kk < k; kk += 8) {
-      const f32x4 v = gemv_load4<BH>(b, (int64_t)kk * ldb + col);
-      const float av = gemv_load1<AH>(a, (int64_t)kk * astride);
+      const f32x4 v = gload4t<BH>(b, (int64_t)kk * ldb + col);
+      const float av = gload1t<AH>(a, (int64_t)kk * astride);
 #pragma unroll
       for (int e = 0; e < 4; ++e) s[e] = __fmaf_rn(av, v[e], s[e]);
     }
   } else {
     for (int kk = rg; kk < k; kk += 8) {
-      const float av = gemv_load1<AH>(a, (int64_t)kk * astride);
+      const float av = gload1t<AH>(a, (int64_t)kk * astride);
 #pragma unroll
       for (int e = 0; e < 4; ++e)
-        if (col + e < n) s[e] = __fmaf_rn(av, gemv_load1<BH>(b, (int64_t)kk * ldb + col + e), s[e]);
+        if (col + e < n) s[e] = __fmaf_rn(av, gload1t<BH>(b, (int64_t)kk * ldb + col + e), s[e]);
     }
   }
   float* red = smem;  // [8][128]
@@ -205,13 +193,17 @@ __device__ inline void gemv_row_tile(const float* a, int64_t astride, const floa
 constexpr int GBK_FAST = 32;  // interior tiles: unguarded loads, two register sets in flight
 constexpr int GEMM_GROUPED_LDS_BYTES = SmemCfg<GBK_FAST>::TOTAL * (int)sizeof(float);
 
-// Interior tiles of 16-byte aligned operands whose k range is a whole number of 32-deep
-// K-tiles run the unguarded, two-register-set K loop of the Newton / statistics kernels and
-// an epilogue with wave-uniform addressing; edge tiles and unaligned operands the guarded
-// BK = 16 loop.  Same products in the same k order: bit-identical results.
-template <int LA, int LB>
+// Interior tiles of aligned operands whose k range is a whole number of 32-deep K-tiles run
+// the unguarded, two-register-set K loop of the Newton / statistics kernels and an epilogue
+// with wave-uniform addressing; edge tiles and unaligned operands the guarded BK = 16 loop.
+// Same products in the same k order: bit-identical results.
+// AH / BH: that operand is stored as bf16 (ps_gemm_grouped_typed).  GTask::a / b then address
+// 2-byte elements and veca / vecb mean "8-byte loads of four elements are legal"; the tile loader
+// widens into the float32 kernel's LDS image (gemm_core.hip.h), everything else is shared.
+template <int LA, int LB, bool AH = false, bool BH = false>
 __global__ __launch_bounds__(256, 2) void gemm_grouped_kernel(const GTask* tasks,
                                                               const GTile* tiles, int ntiles) {
+  static_assert(!(AH && BH), "at most one bf16 operand");
   extern __shared__ __align__(16) float smem[];
   const GTile te = tiles[blockIdx.x];   // dispatch order (common.h deal_to_xcds)
   if (te.task < 0) return;
@@ -219,10 +211,10 @@ __global__ __launch_bounds__(256, 2) void gemm_grouped_kernel(const GTask* tasks
   const int k0 = te.ks * tk.kchunk;
   const int kext = min(tk.kchunk, tk.k - k0);
   // element (mn, k) of a KC operand lies at p[mn*ld + k], of an MC operand at p[k*ld + mn]
-  const float* ap = tk.a + (LA == KC ? (int64_t)k0 : (int64_t)k0 * tk.lda);
-  const float* bp = tk.b + (LB == KC ? (int64_t)k0 : (int64_t)k0 * tk.ldb);
-  Operand A{ap, tk.lda, te.tm * TILE, tk.m, kext, tk.veca != 0};
-  Operand B{bp, tk.ldb, te.tn * TILE, tk.n, kext, tk.vecb != 0};
+  const storage_t<AH>* ap = (const storage_t<AH>*)tk.a + (LA == KC ? (int64_t)k0 : (int64_t)k0 * tk.lda);
+  const storage_t<BH>* bp = (const storage_t<BH>*)tk.b + (LB == KC ? (int64_t)k0 : (int64_t)k0 * tk.ldb);
+  OperandT<storage_t<AH>> A{ap, tk.lda, te.tm * TILE, tk.m, kext, tk.veca != 0};
+  OperandT<storage_t<BH>> B{bp, tk.ldb, te.tn * TILE, tk.n, kext, tk.vecb != 0};
   f32x16 acc[2][2];
   float* out = tk.ksplit > 1 ? tk.partial + (int64_t)te.ks * tk.m * tk.n : tk.c;
   const int ldo = tk.ksplit > 1 ? tk.n : tk.ldc;
@@ -230,8 +222,8 @@ __global__ __launch_bounds__(256, 2) void gemm_grouped_kernel(const GTask* tasks
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   if (LB == MC && tk.m == 1 && tk.ksplit == 1) {
-    gemv_row_tile(tk.a, LA == KC ? 1 : tk.lda, tk.b, tk.ldb, tk.c, tk.n, tk.k, te.tn * TILE,
-                  tk.vecb != 0, smem);
+    gemv_row_tile<AH, BH>(tk.a, LA == KC ? 1 : tk.lda, tk.b, tk.ldb, tk.c, tk.n, tk.k, te.tn * TILE,
+                          tk.vecb != 0, smem);
     return;
   }
   const bool fast = tk.veca != 0 && tk.vecb != 0 && kext % GBK_FAST == 0 &&
@@ -252,74 +244,6 @@ __global__ __launch_bounds__(256, 2) void gemm_grouped_kernel(const GTask* tasks
     return;
   }
   gemm_tile<LA, LB, GBK, true>(A, B, kext, smem, acc);
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = te.tm * TILE + acc_row(wm, i, r, lane);
-        const int col = te.tn * TILE + acc_col(wn, j, lane);
-        if (row < tk.m && col < tk.n) gstore1(out + (int64_t)row * ldo + col, acc[i][j][r]);
-      }
-}
-
-// The same tile with ONE operand stored as bf16 (ps_gemm_grouped_typed): the widening loader of
-// gemm_core_widen.hip.h writes the float32 kernel's LDS image for that operand, the other operand,
-// the K loops' tile order and the epilogues are the float32 kernel's.  GTask::a / b address 2-byte
-// elements where AH / BH says so; veca / vecb then mean "8-byte loads of four elements are legal".
-template <int LA, int LB, bool AH, bool BH>
-__global__ __launch_bounds__(256, 2) void gemm_grouped_kernel_typed(const GTask* tasks,
-                                                                    const GTile* tiles, int ntiles) {
-  static_assert(AH != BH, "exactly one bf16 operand");
-  extern __shared__ __align__(16) float smem[];
-  const GTile te = tiles[blockIdx.x];
-  if (te.task < 0) return;
-  const GTask tk = tasks[te.task];
-  const int k0 = te.ks * tk.kchunk;
-  const int kext = min(tk.kchunk, tk.k - k0);
-  const int64_t aoff = LA == KC ? (int64_t)k0 : (int64_t)k0 * tk.lda;
-  const int64_t boff = LB == KC ? (int64_t)k0 : (int64_t)k0 * tk.ldb;
-  using OpA = typename std::conditional<AH, OperandH, Operand>::type;
-  using OpB = typename std::conditional<BH, OperandH, Operand>::type;
-  using TA = typename std::conditional<AH, uint16_t, float>::type;
-  using TB = typename std::conditional<BH, uint16_t, float>::type;
-  OpA A{(const TA*)tk.a + aoff, tk.lda, te.tm * TILE, tk.m, kext, tk.veca != 0};
-  OpB B{(const TB*)tk.b + boff, tk.ldb, te.tn * TILE, tk.n, kext, tk.vecb != 0};
-  f32x16 acc[2][2];
-  float* out = tk.ksplit > 1 ? tk.partial + (int64_t)te.ks * tk.m * tk.n : tk.c;
-  const int ldo = tk.ksplit > 1 ? tk.n : tk.ldc;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  if (LB == MC && tk.m == 1 && tk.ksplit == 1) {
-    gemv_row_tile<AH, BH>(tk.a, LA == KC ? 1 : tk.lda, tk.b, tk.ldb, tk.c, tk.n, tk.k, te.tn * TILE,
-                          tk.vecb != 0, smem);
-    return;
-  }
-  const bool fast = tk.veca != 0 && tk.vecb != 0 && kext % GBK_FAST == 0 &&
-                    (te.tm + 1) * TILE <= tk.m && (te.tn + 1) * TILE <= tk.n;
-  zero_acc(acc);
-  if (fast) {
-    using LdA = typename std::conditional<AH, TileLoaderH<LA, GBK_FAST, false>, LdF32<LA, GBK_FAST, false>>::type;
-    using LdB = typename std::conditional<BH, TileLoaderH<LB, GBK_FAST, false>, LdF32<LB, GBK_FAST, false>>::type;
-    gemm_tile_accum_ld<LdA, LdB, LA, LB, GBK_FAST, true>(A, B, kext, smem, acc);
-    const int lane_off = 4 * (lane >> 5) * ldo + (lane & 31);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        float* blk = out + (int64_t)(te.tm * TILE + wm * 64 + i * 32) * ldo + te.tn * TILE +
-                     wn * 64 + j * 32;
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          gstore1(blk + (int64_t)((r & 3) + 8 * (r >> 2)) * ldo + lane_off, acc[i][j][r]);
-      }
-    return;
-  }
-  using LgA = typename std::conditional<AH, TileLoaderH<LA, GBK, true>, LdF32<LA, GBK, true>>::type;
-  using LgB = typename std::conditional<BH, TileLoaderH<LB, GBK, true>, LdF32<LB, GBK, true>>::type;
-  gemm_tile_accum_ld<LgA, LgB, LA, LB, GBK, false>(A, B, kext, smem, acc);
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -492,8 +416,8 @@ static int gplan_build(hipStream_t st, const ps_gemm_desc* desc, int count, void
   static const bool lds_ok = [] {
     const void* ks[6] = {(const void*)gemm_grouped_kernel<KC, MC>, (const void*)gemm_grouped_kernel<KC, KC>,
                          (const void*)gemm_grouped_kernel<MC, MC>, (const void*)gemm_grouped_kernel<MC, KC>,
-                         (const void*)gemm_grouped_kernel_typed<MC, MC, true, false>,
-                         (const void*)gemm_grouped_kernel_typed<KC, MC, false, true>};
+                         (const void*)gemm_grouped_kernel<MC, MC, true, false>,
+                         (const void*)gemm_grouped_kernel<KC, MC, false, true>};
     for (const void* k : ks)
       (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 GEMM_GROUPED_LDS_BYTES);
@@ -503,48 +427,33 @@ static int gplan_build(hipStream_t st, const ps_gemm_desc* desc, int count, void
   return PS_OK;
 }
 
-static int gplan_launch(hipStream_t st, const ps_gemm_plan& pl) {
+// Layout group G of a plan: its tiles, then the sum over the K splits where there are any.
+template <int LA, int LB, bool AH = false, bool BH = false>
+static void gplan_launch_group(hipStream_t st, const ps_gemm_plan& pl, int G) {
+  if (pl.ntiles[G] == 0) return;
   const dim3 blk(256);
-  if (pl.a_dtype == PS_DTYPE_BF16 || pl.b_dtype == PS_DTYPE_BF16) {
-    // gplan_build admitted one layout group: 2 (transa = 1, A bf16) or 0 (transa = transb = 0, B bf16)
-    const int G = pl.a_dtype == PS_DTYPE_BF16 ? 2 : 0;
-    if (pl.ntiles[G] > 0) {
-      if (G == 2)
-        hipLaunchKernelGGL((gemm_grouped_kernel_typed<MC, MC, true, false>), dim3((unsigned)pl.ntiles[G]),
-                           blk, GEMM_GROUPED_LDS_BYTES, st, pl.dt[G], pl.dl[G], pl.ntiles[G]);
-      else
-        hipLaunchKernelGGL((gemm_grouped_kernel_typed<KC, MC, false, true>), dim3((unsigned)pl.ntiles[G]),
-                           blk, GEMM_GROUPED_LDS_BYTES, st, pl.dt[G], pl.dl[G], pl.ntiles[G]);
-      if (pl.nsplit[G] > 0)
-        hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3((unsigned)pl.nsplit[G], 256), blk, 0, st,
-                           pl.dt[G], pl.di[G]);
-    }
-    PS_LAUNCH_CHECK();
-    return PS_OK;
-  }
-#define PS_GG(G, LA, LB)                                                                   \
-  if (pl.ntiles[G] > 0) {                                                                  \
-    hipLaunchKernelGGL((gemm_grouped_kernel<LA, LB>), dim3((unsigned)pl.ntiles[G]), blk,   \
-                       GEMM_GROUPED_LDS_BYTES, st, pl.dt[G], pl.dl[G], pl.ntiles[G]);      \
-    if (pl.nsplit[G] > 0)                                                                  \
-      hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3((unsigned)pl.nsplit[G], 256), blk, 0, \
-                         st, pl.dt[G], pl.di[G]);                                          \
-  }
-  PS_GG(0, KC, MC);
-  PS_GG(1, KC, KC);
-  PS_GG(2, MC, MC);
-  PS_GG(3, MC, KC);
-#undef PS_GG
-  PS_LAUNCH_CHECK();
-  return PS_OK;
+  hipLaunchKernelGGL((gemm_grouped_kernel<LA, LB, AH, BH>), dim3((unsigned)pl.ntiles[G]), blk,
+                     GEMM_GROUPED_LDS_BYTES, st, pl.dt[G], pl.dl[G], pl.ntiles[G]);
+  if (pl.nsplit[G] > 0)
+    hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3((unsigned)pl.nsplit[G], 256), blk, 0, st,
+                       pl.dt[G], pl.di[G]);
 }
 
-extern "C" int ps_gemm_grouped_f32(void* stream, const ps_gemm_desc* desc, int count,
-                                   void* workspace, size_t workspace_bytes) {
-  PS_DEVICE_CHECK();
-  ps_gemm_plan pl;
-  PS_RC(gplan_build((hipStream_t)stream, desc, count, workspace, workspace_bytes, pl));
-  return gplan_launch((hipStream_t)stream, pl);
+static int gplan_launch(hipStream_t st, const ps_gemm_plan& pl) {
+  // with a bf16 operand gplan_build admitted one layout group: 2 (transa = 1, A bf16) or
+  // 0 (transa = transb = 0, B bf16)
+  if (pl.a_dtype == PS_DTYPE_BF16) {
+    gplan_launch_group<MC, MC, true, false>(st, pl, 2);
+  } else if (pl.b_dtype == PS_DTYPE_BF16) {
+    gplan_launch_group<KC, MC, false, true>(st, pl, 0);
+  } else {
+    gplan_launch_group<KC, MC>(st, pl, 0);
+    gplan_launch_group<KC, KC>(st, pl, 1);
+    gplan_launch_group<MC, MC>(st, pl, 2);
+    gplan_launch_group<MC, KC>(st, pl, 3);
+  }
+  PS_LAUNCH_CHECK();
+  return PS_OK;
 }
 
 extern "C" int ps_gemm_grouped_typed(void* stream, const ps_gemm_desc* desc, int count, int a_dtype,
@@ -558,6 +467,12 @@ extern "C" int ps_gemm_grouped_typed(void* stream, const ps_gemm_desc* desc, int
   pl.b_dtype = b_dtype;
   PS_RC(gplan_build((hipStream_t)stream, desc, count, workspace, workspace_bytes, pl));
   return gplan_launch((hipStream_t)stream, pl);
+}
+
+extern "C" int ps_gemm_grouped_f32(void* stream, const ps_gemm_desc* desc, int count,
+                                   void* workspace, size_t workspace_bytes) {
+  return ps_gemm_grouped_typed(stream, desc, count, PS_DTYPE_F32, PS_DTYPE_F32, workspace,
+                               workspace_bytes);
 }
 
 extern "C" int ps_gemm_grouped_plan_create(void* stream, const ps_gemm_desc* desc, int count,

@@ -164,7 +164,7 @@ __device__ inline int encode1(float x, float bs_nonzero);
 // the sixteen loads of a lane are then issued one after the other (measured: half the rate of the same
 // stream without the tests, tools/bench_stream.hip).
 template <int MODE, bool FULL, int BITS>
-__device__ __forceinline__ void quant_flat_body(const QTensor* t, int local, unsigned* s_max) {
+__device__ __forceinline__ void quant_flat_chunk(const QTensor* t, int local, unsigned* s_max) {
   const int tid = threadIdx.x;
   const long long cols = t->cols, rows = t->rows, total = rows * cols;
   const long long base = (long long)local * QFLAT;
@@ -299,11 +299,11 @@ __global__ __launch_bounds__(256) void quant_flat_kernel(const QTensor* ts, cons
   const bool full = (long long)(local + 1) * QFLAT <= t->rows * cols;
   // (MODE 0 does not depend on the code width)
   if (MODE == 0 || t->bits == 16) {
-    if (full) quant_flat_body<MODE, true, 16>(t, local, s_max);
-    else quant_flat_body<MODE, false, 16>(t, local, s_max);
+    if (full) quant_flat_chunk<MODE, true, 16>(t, local, s_max);
+    else quant_flat_chunk<MODE, false, 16>(t, local, s_max);
   } else {
-    if (full) quant_flat_body<MODE, true, 8>(t, local, s_max);
-    else quant_flat_body<MODE, false, 8>(t, local, s_max);
+    if (full) quant_flat_chunk<MODE, true, 8>(t, local, s_max);
+    else quant_flat_chunk<MODE, false, 8>(t, local, s_max);
   }
   if (MODE == 0) {
     __syncthreads();
@@ -873,11 +873,11 @@ __global__ __launch_bounds__(256) void quant_decode_all_kernel(const QTensor* ts
   const int local = chunk - t->fchunk0;
   const bool full = (long long)(local + 1) * QFLAT <= t->rows * t->cols;
   if (t->bits == 16) {
-    if (full) quant_flat_body<2, true, 16>(t, local, nullptr);
-    else quant_flat_body<2, false, 16>(t, local, nullptr);
+    if (full) quant_flat_chunk<2, true, 16>(t, local, nullptr);
+    else quant_flat_chunk<2, false, 16>(t, local, nullptr);
   } else {
-    if (full) quant_flat_body<2, true, 8>(t, local, nullptr);
-    else quant_flat_body<2, false, 8>(t, local, nullptr);
+    if (full) quant_flat_chunk<2, true, 8>(t, local, nullptr);
+    else quant_flat_chunk<2, false, 8>(t, local, nullptr);
   }
 }
 

@@ -20,7 +20,6 @@
 
 #include "common.h"
 #include "gemm_core.hip.h"
-#include "gemm_core_widen.hip.h"
 
 namespace psk {
 
@@ -129,41 +128,27 @@ __device__ inline void stats_store_mirror_v4(const f32x16 (&acc)[2][2], float* s
 }
 
 // H: the gradient is stored as bf16 (tk.g points at 2-byte elements, ld / seg_stride in elements):
-// the widening loader writes the float32 kernel's LDS image, everything after it is shared.
+// the tile loader of that storage writes the float32 kernel's LDS image, everything after it is
+// shared.
 template <int LAYOUT, bool FAST, bool H = false>
 __device__ __forceinline__ void stats_tile(const StatsTask& tk, int tm, int tn, float w1,
                                            float w2, float* smem) {
+  using Op = OperandT<storage_t<H>>;
+  const storage_t<H>* g = (const storage_t<H>*)tk.g;
   f32x16 acc[2][2];
   zero_acc(acc);
-  if constexpr (H) {
-    using Ld = TileLoaderH<LAYOUT, SBK, !FAST>;
-    const uint16_t* g = (const uint16_t*)tk.g;
-    if (tk.nseg == 1) {   // as below: the two-set pipeline stays outside the segment loop
-      OperandH A{g, tk.ld, tm * TILE, tk.d, tk.k, tk.vec != 0};
-      OperandH B{g, tk.ld, tn * TILE, tk.d, tk.k, tk.vec != 0};
-      gemm_tile_accum_ld<Ld, Ld, LAYOUT, LAYOUT, SBK, FAST>(A, B, tk.k, smem, acc);
-    } else {
-#pragma unroll 1
-      for (int s = 0; s < tk.nseg; ++s) {
-        const uint16_t* base = g + (int64_t)s * tk.seg_stride;
-        OperandH A{base, tk.ld, tm * TILE, tk.d, tk.k, tk.vec != 0};
-        OperandH B{base, tk.ld, tn * TILE, tk.d, tk.k, tk.vec != 0};
-        gemm_tile_accum_ld<Ld, Ld, LAYOUT, LAYOUT, SBK, false>(A, B, tk.k, smem, acc);
-      }
-    }
-  } else
   // nseg == 1 (every matrix-shaped block) outside the segment loop: the loop around the
   // two-register-set pipeline costs ~100 spilled VGPRs, which only rank>2 blocks then pay
   if (tk.nseg == 1) {
-    Operand A{tk.g, tk.ld, tm * TILE, tk.d, tk.k, tk.vec != 0};
-    Operand B{tk.g, tk.ld, tn * TILE, tk.d, tk.k, tk.vec != 0};
+    Op A{g, tk.ld, tm * TILE, tk.d, tk.k, tk.vec != 0};
+    Op B{g, tk.ld, tn * TILE, tk.d, tk.k, tk.vec != 0};
     gemm_tile_accum<LAYOUT, LAYOUT, SBK, !FAST, FAST>(A, B, tk.k, smem, acc);
   } else {
 #pragma unroll 1
     for (int s = 0; s < tk.nseg; ++s) {
-      const float* base = tk.g + (int64_t)s * tk.seg_stride;
-      Operand A{base, tk.ld, tm * TILE, tk.d, tk.k, tk.vec != 0};
-      Operand B{base, tk.ld, tn * TILE, tk.d, tk.k, tk.vec != 0};
+      const storage_t<H>* base = g + (int64_t)s * tk.seg_stride;
+      Op A{base, tk.ld, tm * TILE, tk.d, tk.k, tk.vec != 0};
+      Op B{base, tk.ld, tn * TILE, tk.d, tk.k, tk.vec != 0};
       gemm_tile_accum<LAYOUT, LAYOUT, SBK, !FAST, false>(A, B, tk.k, smem, acc);
     }
   }
@@ -224,13 +209,6 @@ __device__ __forceinline__ void stats_tile_any(const StatsTask& tk, int tm, int 
     stats_tile<LAYOUT, false, H>(tk, tm, tn, w1, w2, smem);
 }
 
-// element i of the gradient as float32 (H: stored as bf16)
-template <bool H>
-__device__ __forceinline__ float stats_gload(const float* g, int64_t i) {
-  if constexpr (H) return gload1h((const uint16_t*)g + i);
-  else return gload1(g + i);
-}
-
 // Statistic of a vector block (k = 1: biases, scales): S = w1*S + w2 * g g^T is one product per
 // element, fl(g_i * g_j) -- exactly what the MFMA path returns for a single k -- so the tile is
 // streamed by the VALU (16-byte accesses where the statistic allows them) without the LDS
@@ -245,7 +223,7 @@ __device__ inline void stats_vector_tile(const StatsTask& tk, int rt, int ct, fl
   float gc[4];
 #pragma unroll
   for (int e = 0; e < 4; ++e)
-    gc[e] = c + e < tk.d ? stats_gload<H>(tk.g, (int64_t)(c + e) * estride) : 0.f;
+    gc[e] = c + e < tk.d ? gload1t<H>(tk.g, (int64_t)(c + e) * estride) : 0.f;
   const bool v4 = tk.svec != 0 && c + 3 < tk.d;
   if (v4 && (rt + 1) * TILE <= tk.d) {
     // whole rows in range: 8 loads in flight per lane (the workgroup count per CU is set by
@@ -257,7 +235,7 @@ __device__ inline void stats_vector_tile(const StatsTask& tk, int rt, int ct, fl
 #pragma unroll
       for (int p = 0; p < 8; ++p) {
         const int r = rt * TILE + (half * 8 + p) * 8 + (tid >> 5);
-        gr[p] = stats_gload<H>(tk.g, (int64_t)r * estride);
+        gr[p] = gload1t<H>(tk.g, (int64_t)r * estride);
         old[p] = gload4(tk.sin + (int64_t)r * tk.lds + c);
       }
 #pragma unroll
@@ -276,7 +254,7 @@ __device__ inline void stats_vector_tile(const StatsTask& tk, int rt, int ct, fl
   for (int p = 0; p < 16; ++p) {
     const int r = rt * TILE + p * 8 + (tid >> 5);
     if (r >= tk.d) break;
-    const float gr = stats_gload<H>(tk.g, (int64_t)r * estride);
+    const float gr = gload1t<H>(tk.g, (int64_t)r * estride);
     const int64_t o = (int64_t)r * tk.lds + c;
     if (v4) {
       const f32x4 old = gload4(tk.sin + o);
@@ -298,6 +276,8 @@ __device__ inline void stats_vector_tile(const StatsTask& tk, int rt, int ct, fl
 // vector statistics (the branch is uniform per workgroup).  The tile list arrives in hardware
 // dispatch order: workgroup b runs on XCD b % 8, and the host has dealt the statistics over
 // the 8 XCDs by cost (make_tile_list), padding the shorter lists with task = -1.
+// H: the tree's gradients are stored as bf16 (ps_stats_update_grouped_typed).
+template <bool H>
 __global__ __launch_bounds__(256, 2) void stats_grouped_kernel(const StatsTask* tasks,
                                                                const StatsTile* tiles,
                                                                int ntiles, float w1,
@@ -307,31 +287,12 @@ __global__ __launch_bounds__(256, 2) void stats_grouped_kernel(const StatsTask* 
   if (te.task < 0) return;
   const StatsTask tk = tasks[te.task];
   if (tk.k == 1 && tk.nseg == 1) {
-    stats_vector_tile(tk, te.tm, te.tn, w1, w2);
-    if (te.tm != te.tn) stats_vector_tile(tk, te.tn, te.tm, w1, w2);
+    stats_vector_tile<H>(tk, te.tm, te.tn, w1, w2);
+    if (te.tm != te.tn) stats_vector_tile<H>(tk, te.tn, te.tm, w1, w2);
   } else if (tk.layout == KC) {
-    stats_tile_any<KC>(tk, te.tm, te.tn, w1, w2, smem);
+    stats_tile_any<KC, H>(tk, te.tm, te.tn, w1, w2, smem);
   } else {
-    stats_tile_any<MC>(tk, te.tm, te.tn, w1, w2, smem);
-  }
-}
-
-// The same launch for a tree whose gradients are stored as bf16 (ps_stats_update_grouped_typed).
-__global__ __launch_bounds__(256, 2) void stats_grouped_kernel_bf16(const StatsTask* tasks,
-                                                                    const StatsTile* tiles,
-                                                                    int ntiles, float w1,
-                                                                    float w2) {
-  extern __shared__ __align__(16) float smem[];
-  const StatsTile te = tiles[blockIdx.x];
-  if (te.task < 0) return;
-  const StatsTask tk = tasks[te.task];
-  if (tk.k == 1 && tk.nseg == 1) {
-    stats_vector_tile<true>(tk, te.tm, te.tn, w1, w2);
-    if (te.tm != te.tn) stats_vector_tile<true>(tk, te.tn, te.tm, w1, w2);
-  } else if (tk.layout == KC) {
-    stats_tile_any<KC, true>(tk, te.tm, te.tn, w1, w2, smem);
-  } else {
-    stats_tile_any<MC, true>(tk, te.tm, te.tn, w1, w2, smem);
+    stats_tile_any<MC, H>(tk, te.tm, te.tn, w1, w2, smem);
   }
 }
 
@@ -417,8 +378,8 @@ void allow_lds(K kernel) {
 
 void stats_lds_once() {
   static const bool done = [] {
-    allow_lds(stats_grouped_kernel);
-    allow_lds(stats_grouped_kernel_bf16);
+    allow_lds(stats_grouped_kernel<false>);
+    allow_lds(stats_grouped_kernel<true>);
     allow_lds(stats_single_kernel<KC>);
     allow_lds(stats_single_kernel<MC>);
     return true;
@@ -457,14 +418,9 @@ static int stats_update_grouped(void* stream, const ps_stats_desc* desc, int cou
   memcpy(plan.data() + task_bytes, tiles.data(), tile_bytes);
   PS_RC(psh::upload_async(st, d_plan, plan.data(), plan.size()));
   const int nt = (int)tiles.size();
-  if (h)
-    hipLaunchKernelGGL(stats_grouped_kernel_bf16, dim3(nt), dim3(256), STATS_LDS_BYTES, st,
-                       (const StatsTask*)d_plan, (const StatsTile*)(d_plan + task_bytes), nt, w1,
-                       w2);
-  else
-    hipLaunchKernelGGL(stats_grouped_kernel, dim3(nt), dim3(256), STATS_LDS_BYTES, st,
-                       (const StatsTask*)d_plan, (const StatsTile*)(d_plan + task_bytes), nt, w1,
-                       w2);
+  hipLaunchKernelGGL(h ? stats_grouped_kernel<true> : stats_grouped_kernel<false>, dim3(nt),
+                     dim3(256), STATS_LDS_BYTES, st, (const StatsTask*)d_plan,
+                     (const StatsTile*)(d_plan + task_bytes), nt, w1, w2);
   PS_LAUNCH_CHECK();
   return PS_OK;
 }

@@ -77,12 +77,7 @@ __device__ inline float param_sum(const float* slab, int col, const TParam& p, f
 
 // Storage of grad / upd_out (GH) and of param (PH): float32, or bf16 behind the same pointer
 // fields (ps_transform_grads_typed).  A bf16 element widens exactly; the update is rounded to
-// nearest even from the float32 value the float32 kernel stores.
-template <bool H>
-__device__ __forceinline__ float tload(const float* p, int64_t i) {
-  if constexpr (H) return __uint_as_float((uint32_t)(*(const uint16_t PS_GLOBAL*)((const uint16_t*)p + i)) << 16);
-  else return gload1(p + i);
-}
+// nearest even from the float32 value the float32 kernel stores.  Loads: gload1t (gemm_core.hip.h).
 template <bool H>
 __device__ __forceinline__ void tstore(float* p, int64_t i, float v) {
   if constexpr (H) {
@@ -95,8 +90,8 @@ __device__ __forceinline__ void tstore(float* p, int64_t i, float v) {
 
 // pass A: slab[.][0] = sum (graft base)^2 ; slab[.][1] = sum pgrad^2
 template <bool GH>
-__device__ __forceinline__ void transform_pass_a_body(const TParam* params, int count,
-                                                      float* slab, const ps_transform_config& cfg) {
+__global__ __launch_bounds__(256) void transform_pass_a(const TParam* params, int count,
+                                                        float* slab, ps_transform_config cfg) {
   __shared__ float red[4];
   const TChunk ch = find_chunk(params, count, blockIdx.x);
   const TParam p = params[ch.param];
@@ -104,7 +99,7 @@ __device__ __forceinline__ void transform_pass_a_body(const TParam* params, int 
   const int64_t hi = lo + TCHUNK < p.numel ? lo + TCHUNK : p.numel;
   float s0 = 0.f, s1 = 0.f;
   for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
-    const float g = tload<GH>(p.grad, i);
+    const float g = gload1t<GH>(p.grad, i);
     float base = g;
     if (cfg.graft_type == G_SQRT_N) base = g > 0.f ? 1.f : (g < 0.f ? -1.f : 0.f);
     s0 += base * base;
@@ -118,15 +113,6 @@ __device__ __forceinline__ void transform_pass_a_body(const TParam* params, int 
   }
 }
 
-__global__ __launch_bounds__(256) void transform_pass_a(const TParam* params, int count,
-                                                        float* slab, ps_transform_config cfg) {
-  transform_pass_a_body<false>(params, count, slab, cfg);
-}
-__global__ __launch_bounds__(256) void transform_pass_a_bf16(const TParam* params, int count,
-                                                             float* slab, ps_transform_config cfg) {
-  transform_pass_a_body<true>(params, count, slab, cfg);
-}
-
 // Diagonal grafting update before lr / clipping (DS:3502-3528).
 __device__ inline float diag_graft(float g, float gden, float diag, int graft, float w1,
                                    float w2, float eps, float& new_diag) {
@@ -138,8 +124,8 @@ __device__ inline float diag_graft(float g, float gden, float diag, int graft, f
 
 // pass B (Adagrad/RMSProp only): slab[.][2] = sum u^2 of the unclipped update
 template <bool GH>
-__device__ __forceinline__ void transform_pass_b_body(const TParam* params, int count,
-                                                      float* slab, const ps_transform_config& cfg) {
+__global__ __launch_bounds__(256) void transform_pass_b(const TParam* params, int count,
+                                                        float* slab, ps_transform_config cfg) {
   __shared__ float red[4];
   const TChunk ch = find_chunk(params, count, blockIdx.x);
   const TParam p = params[ch.param];
@@ -150,7 +136,7 @@ __device__ __forceinline__ void transform_pass_b_body(const TParam* params, int 
   float s = 0.f;
   for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
     float nd;
-    const float u = diag_graft(tload<GH>(p.grad, i), gscale, gload1(p.diag_in + i), cfg.graft_type,
+    const float u = diag_graft(gload1t<GH>(p.grad, i), gscale, gload1(p.diag_in + i), cfg.graft_type,
                                cfg.beta2_w1, cfg.beta2_w2, cfg.diagonal_epsilon, nd);
     s += u * u;
   }
@@ -158,19 +144,10 @@ __device__ __forceinline__ void transform_pass_b_body(const TParam* params, int 
   if (threadIdx.x == 0) slab[(int64_t)(p.chunk0 + ch.idx) * 4 + 2] = s;
 }
 
-__global__ __launch_bounds__(256) void transform_pass_b(const TParam* params, int count,
-                                                        float* slab, ps_transform_config cfg) {
-  transform_pass_b_body<false>(params, count, slab, cfg);
-}
-__global__ __launch_bounds__(256) void transform_pass_b_bf16(const TParam* params, int count,
-                                                             float* slab, ps_transform_config cfg) {
-  transform_pass_b_body<true>(params, count, slab, cfg);
-}
-
-// pass C: everything else, elementwise
+// pass C: everything else, elementwise.  <storage of grad / upd_out, storage of param>
 template <bool GH, bool PH>
-__device__ __forceinline__ void transform_pass_c_body(const TParam* params, int count,
-                                                      const float* slab, const ps_transform_config& cfg) {
+__global__ __launch_bounds__(256) void transform_pass_c(const TParam* params, int count,
+                                                        const float* slab, ps_transform_config cfg) {
   __shared__ float red[4];
   const TChunk ch = find_chunk(params, count, blockIdx.x);
   const TParam p = params[ch.param];
@@ -202,7 +179,7 @@ __device__ __forceinline__ void transform_pass_c_body(const TParam* params, int 
   const int64_t lo = (int64_t)ch.idx * TCHUNK;
   const int64_t hi = lo + TCHUNK < p.numel ? lo + TCHUNK : p.numel;
   for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
-    const float g = tload<GH>(p.grad, i);
+    const float g = gload1t<GH>(p.grad, i);
     float gu;
     if (has_diag(graft)) {
       float nd;
@@ -219,7 +196,7 @@ __device__ __forceinline__ void transform_pass_c_body(const TParam* params, int 
     const float pg = p.pgrad ? gload1(p.pgrad + i) : gu;
     float su = pg * mult;  // shampoo_update
     float sw = su, gw = gu;
-    const float prm = (coupled_wd || dec_wd) ? tload<PH>(p.param, i) : 0.f;
+    const float prm = (coupled_wd || dec_wd) ? gload1t<PH>(p.param, i) : 0.f;
     if (coupled_wd) { sw = su + cfg.weight_decay * prm; gw = gu + cfg.weight_decay * prm; }
     const float smom = gload1(p.mom_in + i) * cfg.beta1 + w * sw;    // DS:3581-3586
     const float gmom = gload1(p.dmom_in + i) * cfg.beta1 + w * gw;
@@ -232,17 +209,6 @@ __device__ __forceinline__ void transform_pass_c_body(const TParam* params, int 
     gstore1(p.mom_out + i, smom);
     gstore1(p.dmom_out + i, gmom);
   }
-}
-
-__global__ __launch_bounds__(256) void transform_pass_c(const TParam* params, int count,
-                                                        const float* slab, ps_transform_config cfg) {
-  transform_pass_c_body<false, false>(params, count, slab, cfg);
-}
-// <storage of grad / upd_out, storage of param>
-template <bool GH, bool PH>
-__global__ __launch_bounds__(256) void transform_pass_c_typed(const TParam* params, int count,
-                                                              const float* slab, ps_transform_config cfg) {
-  transform_pass_c_body<GH, PH>(params, count, slab, cfg);
 }
 
 }  // namespace psk
@@ -298,25 +264,13 @@ static int transform_grads(void* stream, const ps_transform_desc* desc, int coun
   if (ar.overflow) return PS_EWORKSPACE;
   PS_RC(psh::upload_async(st, dp, hp.data(), sizeof(TParam) * count));
   const dim3 grid((unsigned)chunk0), blk(256);
-  if (!gh && !ph) {
-    hipLaunchKernelGGL(transform_pass_a, grid, blk, 0, st, dp, count, slab, *cfg);
-    if (diag) hipLaunchKernelGGL(transform_pass_b, grid, blk, 0, st, dp, count, slab, *cfg);
-    hipLaunchKernelGGL(transform_pass_c, grid, blk, 0, st, dp, count, slab, *cfg);
-  } else {
-    if (gh) {
-      hipLaunchKernelGGL(transform_pass_a_bf16, grid, blk, 0, st, dp, count, slab, *cfg);
-      if (diag) hipLaunchKernelGGL(transform_pass_b_bf16, grid, blk, 0, st, dp, count, slab, *cfg);
-    } else {
-      hipLaunchKernelGGL(transform_pass_a, grid, blk, 0, st, dp, count, slab, *cfg);
-      if (diag) hipLaunchKernelGGL(transform_pass_b, grid, blk, 0, st, dp, count, slab, *cfg);
-    }
-    if (gh && ph)
-      hipLaunchKernelGGL((transform_pass_c_typed<true, true>), grid, blk, 0, st, dp, count, slab, *cfg);
-    else if (gh)
-      hipLaunchKernelGGL((transform_pass_c_typed<true, false>), grid, blk, 0, st, dp, count, slab, *cfg);
-    else
-      hipLaunchKernelGGL((transform_pass_c_typed<false, true>), grid, blk, 0, st, dp, count, slab, *cfg);
-  }
+  const auto pass_a = gh ? transform_pass_a<true> : transform_pass_a<false>;
+  const auto pass_b = gh ? transform_pass_b<true> : transform_pass_b<false>;
+  const auto pass_c = gh ? (ph ? transform_pass_c<true, true> : transform_pass_c<true, false>)
+                         : (ph ? transform_pass_c<false, true> : transform_pass_c<false, false>);
+  hipLaunchKernelGGL(pass_a, grid, blk, 0, st, dp, count, slab, *cfg);
+  if (diag) hipLaunchKernelGGL(pass_b, grid, blk, 0, st, dp, count, slab, *cfg);
+  hipLaunchKernelGGL(pass_c, grid, blk, 0, st, dp, count, slab, *cfg);
   PS_LAUNCH_CHECK();
   return PS_OK;
 }

@@ -678,7 +678,8 @@ int ps_fd_filter_step_f32(void* stream, const float* z, const float* y, const fl
  * next step reads.  c_hi / c_lo: HOST arrays of `batch` <= 16 device pointers to the fragment-major
  * covariances (ps_convert_f32_to_bf16, transpose = 3); yt_hi / yt_lo: the planes of y (written by
  * ps_fd_filter_step_f32 with ldt = 0 or by the previous call; nt_* must be other buffers).
- * n % 128 == 0, b in {32, 64, 96}; PS_EUNSUPPORTED otherwise.  A factor with degree < step: y_next = y.
+ * n % 128 == 0, b in {32, 64, 96}; PS_EUNSUPPORTED otherwise.  A factor with degree < step: y_next = y
+ * and nt_* = yt_* (the planes of y_next, like every other factor's).
  * ps_fd_filter_round_f32 uses it when every desc[j].a_tiled == 2: yt_hi / yt_lo must then hold TWO
  * copies of the planes (2 * batch * n * b elements each); desc[j].b_*, c and ldt are ignored. */
 int ps_fd_cy_step_f32(void* stream, const void* const* c_hi, const void* const* c_lo, int batch,

@@ -387,6 +387,12 @@ __global__ __launch_bounds__(256, 2) void fd_cy_step_kernel(const FdCyArgs a) {
   if (a.step > deg) {                                 // the factor's filter is finished: y' = y
     for (int q = tid; q < ROWS * B / 4; q += 256)
       *(f32x4 PS_GLOBAL*)(a.y_next + blk + 4 * q) = gload4(a.y + blk + 4 * q);
+    // the planes of y_next = y: this block's rows are the same contiguous run of the input planes
+    if (a.nt_hi != nullptr)
+      for (int q = tid; q < ROWS * B / 8; q += 256) {
+        *(u32x4 PS_GLOBAL*)(a.nt_hi + blk + 8 * q) = gload16(a.bt_hi + blk + 8 * q);
+        *(u32x4 PS_GLOBAL*)(a.nt_lo + blk + 8 * q) = gload16(a.bt_lo + blk + 8 * q);
+      }
     return;
   }
   float sigma = sigma1;

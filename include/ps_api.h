@@ -196,7 +196,7 @@ const char* ps_error_string(int code);
  *   eigh_keep_max_cond (struct_size grows: a caller built against the shorter struct gets the default).
  *   Check ps_version() >= 306 before relying on either.
  * The PS_* environment variables of earlier rounds survive only as a developer override, read in
- * ONE function (csrc/options.cpp ps_dev_env_overrides) and only when PS_DEV_ENV=1 is set. */
+ * ONE function (csrc/options.hip ps_dev_env_overrides) and only when PS_DEV_ENV=1 is set. */
 enum { PS_PRODUCTS_F32 = 0, PS_PRODUCTS_BF16X6 = 1, PS_PRODUCTS_BF16X3 = 2 };
 enum { PS_ACCUM_SEGMENTED = 0, PS_ACCUM_CHAIN = 1 };
 enum { PS_EXEC_STAGED = 0, PS_EXEC_PERSISTENT = 1 };

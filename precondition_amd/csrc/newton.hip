@@ -569,25 +569,27 @@ __device__ inline void write_metrics(float* metrics, int b, float err, int it, f
 // ==================================================================================
 // staged execution (PS_NEWTON_PERSISTENT=0)
 // ==================================================================================
-// DEEP = false: 3 workgroups per CU.  DEEP = true: two-K-tile-deep register prefetch, 2 per CU.
+// K tiles of STAGE_BK = 32, the two-K-tile-deep register prefetch of gemm_core.hip.h, 2 workgroups per CU.
+// PIPE: the explicitly software-pipelined K loop (the default; PS_NEWTON_PIPE=0: the compiler-scheduled one).
 // TRACE (dev, PS_NEWTON_TRACE=<file>): one record of 8 x u64 per tile -- launch sequence number,
 // tile index | product << 32, HW_ID | XCC_ID << 32, and the 100 MHz clock at the start of the
 // tile, after its first LDS fill, at the end of its (last) K loop and at its end.
 // CAREFUL: segmented accumulation for the blocks that ask for it (gemm_core.hip.h
 // deep_run_pipe_seg: one register set of loads, the other set's registers hold the segment totals;
 // 251 VGPRs, no spills, two workgroups per CU like the default instantiation).
-template <int BK, bool DEEP, int XM = 0, bool TRACE = false, bool PIPE = false, bool CAREFUL = false>
-__global__ __launch_bounds__(256, CAREFUL ? 2 : ((DEEP && BK == 32) ? 2 : 3)) void newton_stage_kernel(
+constexpr int STAGE_BK = 32;
+template <int XM = 0, bool TRACE = false, bool PIPE = false, bool CAREFUL = false>
+__global__ __launch_bounds__(256, 2) void newton_stage_kernel(
     const NewtonBlock* blocks, NewtonState* states,
-    const TileEntry* tiles, int ntiles, int navg, unsigned long long* trace = nullptr,
+    const TileEntry* tiles, int ntiles, int stagger, unsigned long long* trace = nullptr,
     unsigned trace_seq = 0, unsigned trace_cap = 0) {
-  extern __shared__ __align__(16) float smem[];  // SmemCfg<BK>::TOTAL floats
+  extern __shared__ __align__(16) float smem[];  // SmemCfg<STAGE_BK>::TOTAL floats
   __shared__ unsigned long long s_trace[2];
-  // navg carries the dev stagger word here: (mode << 16) | microseconds.  Co-resident workgroups of
+  // stagger (dev, PS_NEWTON_STAGGER): (mode << 16) | microseconds.  Co-resident workgroups of
   // equal tiles start together and stay in lockstep (prologues, K loops and epilogues coincide);
   // delaying half of the first residents by half a tile de-phases them for the whole launch.
-  if (navg != 0 && blockIdx.x < 512) {
-    const int mode = navg >> 16, us = navg & 0xffff, i0 = blockIdx.x;
+  if (stagger != 0 && blockIdx.x < 512) {
+    const int mode = stagger >> 16, us = stagger & 0xffff, i0 = blockIdx.x;
     // mode 2: the second half of the first residents (the dispatcher fills slot 0 of every CU with
     // workgroups 0 .. 255, then slot 1); modes 0 / 1: other halves, for A/B runs
     const bool late = mode == 2 ? i0 >= 256 : mode == 1 ? ((i0 >> 3) & 1) != 0 : (i0 & 1) != 0;
@@ -617,8 +619,8 @@ __global__ __launch_bounds__(256, CAREFUL ? 2 : ((DEEP && BK == 32) ? 2 : 3)) vo
     }
     // P0 of step 0 (H0 Mi, H0 a scaled identity) was written by newton_init2_tile
     if (st->phase == PH_ACTIVE && !(tk.prod == 0 && st->it == 0))
-      newton_product_item<BK, false, DEEP, XM, PIPE, CAREFUL>(nb, st, tk.prod, st->cur, st->avg_on, te.tm,
-                                                     te.tn, smem, TRACE ? s_trace : nullptr);
+      newton_product_item<STAGE_BK, false, true, XM, PIPE, CAREFUL>(nb, st, tk.prod, st->cur, st->avg_on,
+                                                                   te.tm, te.tn, smem, TRACE ? s_trace : nullptr);
     if (TRACE && threadIdx.x == 0) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the tile's stores have left the CU
       const unsigned long long t3 = __builtin_amdgcn_s_memrealtime();
@@ -678,7 +680,7 @@ __device__ inline void finish_try(NewtonState* st) {
 
 // mode 0: after init2 (enter the inner loop, DS:874-877); mode 1: after one
 // Newton step (DS:848 carry + DS:836-840 condition).
-// ids (may be NULL = blocks 0 .. nblocks - 1): the blocks of one stream group (newton_driver).
+// ids (may be NULL = blocks 0 .. nblocks - 1): the blocks of one stream group (StageGroups).
 __global__ __launch_bounds__(256) void newton_control_kernel(
     NewtonState* states, int nblocks, int mode, int num_iters, float tol, int gen,
     HostStatus* status, float avg_thr, const int* ids = nullptr) {
@@ -1057,10 +1059,10 @@ constexpr bool PERSIST_WT = false;
 template <int BK>
 constexpr int PSMEM = SmemCfg<BK>::TOTAL > 64 * 132 ? SmemCfg<BK>::TOTAL : 64 * 132;
 
-// DEEP = false: 3 workgroups per CU (<= 168 VGPRs).  DEEP = true: two-K-tile-deep register
-// prefetch in the K loop, 2 workgroups per CU (the second register set does not fit in 168).
-template <int BK, bool DEEP, bool CAREFUL = false>
-__global__ __launch_bounds__(256, (DEEP || CAREFUL) ? 2 : 3) void newton_persistent_kernel(PArgs pa) {
+// One register set of global loads and 3 workgroups per CU (<= 168 VGPRs), which cover each
+// other's dequeue / epilogue phases; CAREFUL (segmented accumulation): 2 per CU.
+template <int BK, bool CAREFUL = false>
+__global__ __launch_bounds__(256, CAREFUL ? 2 : 3) void newton_persistent_kernel(PArgs pa) {
   extern __shared__ __align__(16) float smem[];  // PSMEM<BK> floats + 16
   float* scratch = smem + PSMEM<BK>;             // 16 floats of control scratch
   u64* s_item = reinterpret_cast<u64*>(scratch + 12);
@@ -1110,7 +1112,7 @@ __global__ __launch_bounds__(256, (DEEP || CAREFUL) ? 2 : 3) void newton_persist
     NewtonState* st = &pa.states[b];
     if (kind == IT_PROD) {
       if (!(prod == 0 && ald(&st->it) == 0))   // step-0 P0: written by newton_init2_tile
-        newton_product_item<BK, PERSIST_WT, DEEP, 0, false, CAREFUL>(nb, st, prod, bit, avg, tm, tn, smem,
+        newton_product_item<BK, PERSIST_WT, false, 0, false, CAREFUL>(nb, st, prod, bit, avg, tm, tn, smem,
                                       pa.prof ? s_stamp : nullptr);
     } else if (kind == IT_INIT1) {
       newton_init1_tile<PERSIST_WT>(nb, ald(&st->ridge_try), tm, tn, scratch);
@@ -1206,8 +1208,6 @@ struct Plan {
   // staged execution
   int nstages = 0;
   std::vector<std::vector<TileEntry>> stage_tiles;
-  // the same tiles in the order used while M updates are averaged (two-pass tiles first)
-  std::vector<std::vector<TileEntry>> stage_tiles_avg;
   std::vector<TileEntry> init_tiles;  // one per (block, tile)
   // stream groups (staged execution): the tile lists above are group-major; group g owns the
   // slice [goff[s][g], goff[s][g + 1]) of stage s (ioff: of the init list) and the blocks gids[g]
@@ -1230,7 +1230,50 @@ constexpr int MAX_GROUPS = 4;
 // persistent kernel (no host round trip at all: the call only enqueues).
 // (selected per call: ps_options.execution)
 
-// groups: stream groups of the staged execution (newton_driver); weight (may be NULL): relative number of
+// Persistent execution: block -> queue, queue capacity.  A workgroup serves ONE queue
+// (blockIdx % nq), so the queues must carry equal work: blocks are dealt by longest-
+// processing-time on c(p) * T^3 for every queue count 1..8 and the count with the smallest
+// makespan (max queue load x queue count; ties -> more queues, for L2 locality) is used.
+void plan_queues(Plan& pl, const int32_t* n) {
+  const int batch = pl.batch;
+  std::vector<int> order;
+  for (int b = 0; b < batch; ++b) if (pl.n_eff[b] >= 1) order.push_back(b);
+  auto cost = [&](int b) {
+    const double t = pl.npad[b] / (double)TILE;
+    return (double)pl.chains[b].size() * t * t * t;
+  };
+  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return cost(x) > cost(y); });
+  double best = -1.0;
+  std::vector<int> assign(batch, 0);
+  for (int nq = NQ; nq >= 1; --nq) {
+    double load[NQ] = {0};
+    for (int b : order) {
+      int q = 0;
+      for (int k = 1; k < nq; ++k) if (load[k] < load[q]) q = k;
+      assign[b] = q;
+      load[q] += cost(b);
+    }
+    double mx = 0;
+    for (int k = 0; k < nq; ++k) mx = std::max(mx, load[k]);
+    if (best < 0 || mx * nq < best * (1.0 - 1e-9)) {
+      best = mx * nq;
+      pl.nq = nq;
+      pl.queue_of = assign;
+    }
+  }
+  size_t cap[NQ] = {0};
+  for (int b : order) {
+    const size_t t = pl.npad[b] / TILE, tc = (n[b] + TILE - 1) / TILE;
+    cap[pl.queue_of[b]] += std::max(2 * t * t, tc * tc);  // most items a block can have outstanding
+  }
+  size_t need = 64;
+  for (int k = 0; k < NQ; ++k) need = std::max(need, cap[k] + 64 + 4096);  // + exit tokens
+  size_t c = 64;
+  while (c < need) c <<= 1;
+  pl.qcap = c;
+}
+
+// groups: stream groups of the staged execution (StageGroups); weight (may be NULL): relative number of
 // Newton steps a block is expected to take (the caller's iteration-count hint) for balancing them.
 void make_plan(Plan& pl, int batch, const int32_t* n, const int32_t* p,
                const int32_t* padding_start, bool staged, int groups = 1,
@@ -1261,47 +1304,7 @@ void make_plan(Plan& pl, int batch, const int32_t* n, const int32_t* p,
   }
   pl.pip.build(batch, pl.n_eff);
 
-  // ---- persistent execution: block -> queue, queue capacity.  A workgroup serves ONE queue
-  // (blockIdx % nq), so the queues must carry equal work: blocks are dealt by longest-
-  // processing-time on c(p) * T^3 for every queue count 1..8 and the count with the smallest
-  // makespan (max queue load x queue count; ties -> more queues, for L2 locality) is used.
-  {
-    std::vector<int> order;
-    for (int b = 0; b < batch; ++b) if (pl.n_eff[b] >= 1) order.push_back(b);
-    auto cost = [&](int b) {
-      const double t = pl.npad[b] / (double)TILE;
-      return (double)pl.chains[b].size() * t * t * t;
-    };
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return cost(x) > cost(y); });
-    double best = -1.0;
-    std::vector<int> assign(batch, 0);
-    for (int nq = NQ; nq >= 1; --nq) {
-      double load[NQ] = {0};
-      for (int b : order) {
-        int q = 0;
-        for (int k = 1; k < nq; ++k) if (load[k] < load[q]) q = k;
-        assign[b] = q;
-        load[q] += cost(b);
-      }
-      double mx = 0;
-      for (int k = 0; k < nq; ++k) mx = std::max(mx, load[k]);
-      if (best < 0 || mx * nq < best * (1.0 - 1e-9)) {
-        best = mx * nq;
-        pl.nq = nq;
-        pl.queue_of = assign;
-      }
-    }
-    size_t cap[NQ] = {0};
-    for (int b : order) {
-      const size_t t = pl.npad[b] / TILE, tc = (n[b] + TILE - 1) / TILE;
-      cap[pl.queue_of[b]] += std::max(2 * t * t, tc * tc);  // most items a block can have outstanding
-    }
-    size_t need = 64;
-    for (int k = 0; k < NQ; ++k) need = std::max(need, cap[k] + 64 + 4096);  // + exit tokens
-    size_t c = 64;
-    while (c < need) c <<= 1;
-    pl.qcap = c;
-  }
+  plan_queues(pl, n);
   if (!staged) return;
 
   // ---- staged execution: stage s runs product s+1 of every block (product 0, the H
@@ -1360,33 +1363,6 @@ void make_plan(Plan& pl, int batch, const int32_t* n, const int32_t* p,
     pl.ioff[g + 1] = (int)pl.init_tiles.size();
     for (int s = 0; s < pl.nstages; ++s) pl.goff[s][g + 1] = (int)pl.stage_tiles[s].size();
   }
-  // Launches of steps that average the M update: the off-diagonal tiles of that product run two
-  // passes (TF_RAW + TF_AVG), twice as long as every other tile of the launch.  Workgroup i runs
-  // list entry xcd_remap(i): XCD x walks its contiguous chunk of the list in order, so inside every
-  // chunk the two-pass tiles are moved to the front (longest first: the one-pass tiles fill the
-  // tail of the launch instead of waiting behind it; same tiles per XCD, so a block's operands
-  // stay in one L2).
-  pl.stage_tiles_avg = pl.stage_tiles;
-  for (int s = 0; s < pl.nstages; ++s)
-    for (int g = 0; g < pl.ngroups; ++g) {   // every group's slice is a launch of its own
-      auto& v = pl.stage_tiles_avg[s];
-      const int nt = pl.goff[s][g + 1] - pl.goff[s][g], q = nt >> 3, r = nt & 7;
-      int first = pl.goff[s][g];
-      for (int x = 0; x < 8; ++x) {
-        const int cnt = x < r ? q + 1 : q;
-        std::stable_partition(v.begin() + first, v.begin() + first + cnt, [&](const TileEntry& te) {
-          const int b = te.task & TE_BLOCK_MASK, k = te.task >> 24;
-          return k == (int)pl.chains[b].size() - 1 && te.tm != te.tn;
-        });
-        first += cnt;
-      }
-    }
-}
-
-// dev A/B: PS_NEWTON_GRID=g caps the stage launches at g workgroups that loop over the tile
-// list (0 / unset: one workgroup per tile).
-static int stage_grid(int ntiles, int cap) {
-  return cap > 0 ? std::min(cap, ntiles) : ntiles;
 }
 
 struct WsLayout {
@@ -1396,7 +1372,6 @@ struct WsLayout {
   u64* slots;
   u64* prof;
   TileEntry* tiles[MAX_PROD];
-  TileEntry* tiles_avg[MAX_PROD];
   TileEntry* init_tiles;
   int* group_ids;     // [batch]: the block ids of the stream groups, group-major
   std::vector<float*> mat[10];
@@ -1416,8 +1391,7 @@ size_t carve(Plan& pl, Arena& ar, WsLayout* lo, bool staged) {
   if (staged) {
     for (int s = 0; s < pl.nstages; ++s) {
       TileEntry* e = ar.take<TileEntry>(pl.stage_tiles[s].size());
-      TileEntry* e2 = ar.take<TileEntry>(pl.stage_tiles[s].size());
-      if (lo) { lo->tiles[s] = e; lo->tiles_avg[s] = e2; }
+      if (lo) lo->tiles[s] = e;
     }
     TileEntry* it = ar.take<TileEntry>(pl.init_tiles.size());
     int* gi = ar.take<int>(B);
@@ -1447,10 +1421,11 @@ Profile g_prof;
 struct ProfRun {
   struct Span { hipEvent_t a, b; int kind; int count; };  // kind 0 products, 1 power iter, 2 other
   std::vector<Span> spans;
-  bool active;
-  hipStream_t st;
+  bool active = false;
+  hipStream_t st = nullptr;
   hipEvent_t base = nullptr;   // time origin (caller's stream): spans of different streams on one axis
-  explicit ProfRun(hipStream_t s) : active(g_prof.on), st(s) {
+  void start(hipStream_t s) {
+    active = g_prof.on; st = s;
     if (active && (hipEventCreate(&base) != hipSuccess || hipEventRecord(base, st) != hipSuccess)) active = false;
   }
   // count: launches the span brackets (kind 0).  An event record is a queue packet with a
@@ -1502,10 +1477,6 @@ struct ProfRun {
   }
 };
 
-// Side streams of the stream groups: the library's shared pool (common.h psh::side_stream; one device per
-// process: PS_DEVICE_CHECK).
-inline hipStream_t side_stream(int k) { return psh::side_stream(k); }
-
 // One mapped status ring per host thread: a thread runs one call at a time, so calls
 // on distinct (stream, workspace) pairs from different threads never share slots.
 HostStatus* pinned_status() {
@@ -1521,37 +1492,471 @@ HostStatus* pinned_status() {
 // Resident grid of the persistent kernel (workgroups per CU from the occupancy query x
 // CUs).  Correctness does not depend on residency (no workgroup ever waits for a specific
 // other workgroup: waits are for queue items, which only running workgroups produce),
-// so the query is for speed only.
-// Deep-prefetch / 2-per-CU variant of the product kernels.  Staged execution: on by default
-// with BK = 32 (measured, 256 x 512^2 / 64 x 1024^2 product launches: BK16 13.75 / 22.69 ms,
-// BK16+deep 13.73 / 22.39, BK32 14.51 / 22.76, BK32+deep 13.57 / 21.70).  Persistent execution:
-// off by default (3 workgroups per CU cover each other's dequeue / epilogue phases better).
-// PS_NEWTON_DEEP = 0 | 1 and PS_NEWTON_BK = 16 | 32 override.
-int persistent_grid(size_t lds_bytes, bool deep, int wg_per_cu) {
+// so the query is for speed only (of the instantiation that will be launched: careful = segmented accumulation).
+int persistent_grid(size_t lds_bytes, bool careful) {
   static int grid[2] = {0, 0};
-  if (grid[deep] == 0) {
-    int dev = 0, cus = 256, occ = deep ? 2 : 3;
+  if (grid[careful] == 0) {
+    int dev = 0, cus = 256, occ = careful ? 2 : 3;
     (void)hipGetDevice(&dev);
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
       cus = prop.multiProcessorCount;
-    const void* fn = deep ? (const void*)newton_persistent_kernel<NBK, true>
-                          : (const void*)newton_persistent_kernel<NBK, false>;
+    const void* fn = careful ? (const void*)newton_persistent_kernel<NBK, true>
+                             : (const void*)newton_persistent_kernel<NBK, false>;
     int q = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, fn, 256, lds_bytes) == hipSuccess && q >= 1)
       occ = q;
-    if (wg_per_cu > 0) occ = wg_per_cu;
-    grid[deep] = cus * occ;
+    grid[careful] = cus * occ;
   }
-  return grid[deep];
+  return grid[careful];
+}
+
+// What one call works with: the caller's arguments (newton_driver's, in its order), the resolved options,
+// the plan, the workspace layout, the host copies of the descriptors and the profiler.
+struct NewtonCall {
+  hipStream_t st;
+  const float* const* a;
+  const int32_t *n, *lda, *p, *padding_start;
+  int batch, num_iters;
+  float ridge_epsilon, error_tolerance;
+  int relative_matrix_epsilon;
+  const float* max_ev_given; int symmetry;
+  float* const* out; const int32_t* ldo; float* metrics;
+  void* workspace; size_t workspace_bytes;
+  psh::Options opt;
+  bool staged = true;
+  int stagger = 0;            // the stage kernels' de-phasing word, (mode << 16) | microseconds
+  bool any_careful = false;   // a live block asks for segmented accumulation
+  Plan pl; WsLayout lo;
+  std::vector<NewtonBlock> hb; std::vector<NewtonState> hs;
+  ProfRun prof;
+  unsigned pi_expired_before = PiPlan::expired_total();   // (of the resident power iteration, before this call's)
+};
+
+// Argument checks, the defaults that depend on the call's blocks (stream groups, stagger), plan and layout.
+int validate_and_plan(NewtonCall& c) {
+  const int batch = c.batch;
+  if (batch <= 0 || !c.a || !c.n || !c.lda || !c.p || !c.out || !c.ldo || !c.metrics || !c.workspace ||
+      c.num_iters < 1 || c.symmetry < PS_SYMMETRY_VERIFY || c.symmetry > PS_SYMMETRY_GENERAL)
+    return PS_EINVAL;
+  if (batch > 65535) return PS_EUNSUPPORTED;  // 16-bit block field of a queue item
+  for (int b = 0; b < batch; ++b)
+    if (c.n[b] < 1 || c.lda[b] < c.n[b] || c.ldo[b] < c.n[b] || !c.a[b] || !c.out[b]) return PS_EINVAL;
+  c.staged = c.opt.execution != PS_EXEC_PERSISTENT;
+  if (c.opt.force_general) c.symmetry = PS_SYMMETRY_GENERAL;   // dev
+  // Stream groups of the staged execution (see StageGroups below): 2 by default when the call has
+  // work for them (PS_NEWTON_GROUPS / psh::Options::newton_groups: 1 = the single-stream execution).
+  // Measured (tools/dev_stage_variants.py groups, profiles/r06_newton_stream_groups.txt): calls whose
+  // blocks differ in size or exponent (a ViT-B tree: 139.6 -> 133.9 ms with 2 groups, 135-136 with 3 / 4)
+  // gain; homogeneous batches do not (256 x 512^2: 16.1 vs 16.2-16.3 ms, 64 x 1024^2: 23.5 vs 23.7 -- their
+  // launches are whole rounds of equal tiles and the second stream only costs L2 locality), so the default
+  // is 2 groups for mixed calls and 1 otherwise.
+  int want_groups = c.opt.newton_groups;
+  if (want_groups <= 0) {
+    want_groups = 1;
+    int n0 = -1, p0 = -1;
+    for (int b = 0; b < batch; ++b) {
+      int ne = c.n[b];
+      if (c.padding_start) ne = std::max(0, std::min(ne, (int)c.padding_start[b]));
+      if (ne < 1) continue;
+      const int np_ = psh::round_up(ne, TILE);
+      if (n0 < 0) { n0 = np_; p0 = c.p[b]; }
+      else if (np_ != n0 || c.p[b] != p0) { want_groups = 2; break; }
+    }
+  }
+  if (!c.staged || c.opt.newton_trace) want_groups = 1;
+  Plan& pl = c.pl;
+  make_plan(pl, batch, c.n, c.p, c.padding_start, c.staged, want_groups, c.opt.iters_hint, c.opt.iters_hint_stride);
+  if (!pl.ok) return PS_EUNSUPPORTED;
+  if (pl.max_n > 16384) return PS_EUNSUPPORTED;
+  // De-phasing of co-resident workgroups (newton_stage_kernel): measured 64 x 1024^2: 21.6 -> 20.9 ms
+  // (-2 ... -5 % by box), no effect at 512^2 (a tile is too short for the delay to pay) or on the
+  // mixed tile lengths of a ViT-B launch: on by itself only when every tile of the call has K >= 1024.
+  int min_npad = 1 << 30;
+  for (int b = 0; b < batch; ++b)
+    if (!pl.chains[b].empty()) min_npad = std::min(min_npad, pl.npad[b]);
+  c.stagger = c.opt.stagger >= 0 ? c.opt.stagger : (min_npad >= 1024 && min_npad < (1 << 30) ? ((2 << 16) | 25) : 0);
+  pl.pip.set_options(c.opt);
+  Arena ar(c.workspace, c.workspace_bytes);
+  carve(pl, ar, &c.lo, c.staged);
+  return ar.overflow ? PS_EWORKSPACE : PS_OK;
+}
+
+// Host copies of the per-block descriptors and of the initial loop state; sets any_careful.
+void fill_descriptors(NewtonCall& c) {
+  const Plan& pl = c.pl;
+  const WsLayout& lo = c.lo;
+  const psh::Options& opt = c.opt;
+  // Leading steps of every try whose M update is computed in full and averaged with its
+  // transpose (TileFlags above); per block 0 when the caller's hint marks it well conditioned.
+  const int navg = opt.averaged_steps;
+  const int seg_on = (opt.accumulation == PS_ACCUM_SEGMENTED && opt.products == PS_PRODUCTS_F32) ? 1 : 0;
+  c.hb.resize(c.batch);
+  c.hs.resize(c.batch);
+  for (int b = 0; b < c.batch; ++b) {
+    NewtonBlock& nb = c.hb[b];
+    NewtonState& ns = c.hs[b];
+    memset(&nb, 0, sizeof(nb));
+    memset(&ns, 0, sizeof(ns));
+    nb.a = c.a[b]; nb.out = c.out[b];
+    nb.M[0] = lo.mat[0][b]; nb.M[1] = lo.mat[1][b];
+    nb.H[0] = lo.mat[2][b]; nb.H[1] = lo.mat[3][b];
+    nb.Mi = lo.mat[4][b];
+    for (int k = 0; k < NTEMP; ++k) nb.T[k] = lo.mat[5 + k][b];
+    nb.sumsq_partial = lo.sumsq[b];
+    nb.n = pl.n_eff[b]; nb.n_full = c.n[b]; nb.lda = c.lda[b]; nb.ldo = c.ldo[b];
+    nb.npad = pl.npad[b]; nb.p = c.p[b];
+    nb.alpha = (float)(-1.0 / c.p[b]);      // DS:774 (float32 of the exact quotient)
+    nb.one_minus_alpha = 1.0f - nb.alpha;   // DS:844, float32 subtraction
+    nb.inv_p = (float)(1.0 / c.p[b]);
+    nb.nprod = (int)pl.chains[b].size();
+    nb.queue = pl.queue_of[b];
+    for (size_t k = 0; k < pl.chains[b].size(); ++k) {
+      nb.pa[k] = (short)pl.chains[b][k].a;
+      nb.pb[k] = (short)pl.chains[b][k].b;
+      nb.pc[k] = (short)pl.chains[b][k].c;
+    }
+    ns.phase = pl.n_eff[b] >= 1 ? PH_INIT : PH_DONE;
+    ns.ratio = 1.f;
+    // A block whose hint (its Newton iteration count at the previous recompute) lies in
+    // [1, fast_max_iters] is well conditioned: mirrored M updates are exact to 1e-6 there.  Every
+    // other block (no hint, NaN, a slow block) averages the M update of its first steps.
+    const float hv = opt.iters_hint ? opt.iters_hint[(size_t)b * opt.iters_hint_stride] : 0.f;
+    const bool fast = hv >= 1.f && hv <= (float)opt.fast_max_iters;   // false for NaN
+    ns.navg = fast ? 0 : navg;
+    // the accumulation mode is the call's, not the block's: a block's arithmetic does not depend
+    // on its hint beyond the averaged steps
+    ns.seg = seg_on;
+    if (pl.n_eff[b] >= 1) c.any_careful |= ns.seg != 0;
+  }
+}
+
+// Tile lists and group ids of the staged execution (pinned staging ring: no stream synchronisation).
+int upload_stage_tables(NewtonCall& c) {
+  const Plan& pl = c.pl;
+  for (int s = 0; s < pl.nstages; ++s)
+    PS_RC(psh::upload_async(c.st, c.lo.tiles[s], pl.stage_tiles[s].data(), sizeof(TileEntry) * pl.stage_tiles[s].size()));
+  PS_RC(psh::upload_async(c.st, c.lo.init_tiles, pl.init_tiles.data(), sizeof(TileEntry) * pl.init_tiles.size()));
+  std::vector<int> ids;
+  for (auto& v : pl.gids) ids.insert(ids.end(), v.begin(), v.end());
+  PS_RC(psh::upload_async(c.st, c.lo.group_ids, ids.data(), sizeof(int) * ids.size()));
+  return 0;
+}
+
+// Everything from the descriptor upload to the seeded loop state; run again (on the streaming
+// power iteration) if the resident power iteration reports an expired wait.
+int enqueue_front(NewtonCall& c) {
+  Plan& pl = c.pl;
+  hipStream_t st = c.st;
+  PS_RC(pl.pip.upload(st, c.a, c.lda));  // also fixes pl.pip.d_asym
+  for (int b = 0; b < c.batch; ++b) c.hb[b].asym = pl.pip.d_asym + b;
+  PS_RC(psh::upload_async(st, c.lo.blocks, c.hb.data(), sizeof(NewtonBlock) * c.batch));
+  PS_RC(psh::upload_async(st, c.lo.states, c.hs.data(), sizeof(NewtonState) * c.batch));
+  PS_RC(pl.pip.enqueue_symmetry(st, c.symmetry));
+  // ---- power iteration -> ridge epsilon --------------------------------------
+  c.prof.begin(1);
+  if (c.relative_matrix_epsilon && !c.max_ev_given) PS_RC(pl.pip.enqueue(st, 100, 1e-6f));  // DS:820-825
+  c.prof.end();
+  hipLaunchKernelGGL(newton_setup_kernel, dim3((c.batch + 255) / 256), dim3(256), 0, st, c.lo.states,
+                     pl.pip.d_blocks, c.batch, c.ridge_epsilon, c.relative_matrix_epsilon, c.max_ev_given);
+  PS_LAUNCH_CHECK();
+  return 0;
+}
+
+// dev only (PS_NEWTON_PROF): per-workgroup time split of the persistent kernel.  Waits for the stream.
+int report_persistent_profile(const NewtonCall& c, int grid) {
+  std::vector<u64> h(12 * (size_t)grid);
+  PS_HIP(hipStreamSynchronize(c.st));
+  PS_HIP(hipMemcpy(h.data(), c.lo.prof, sizeof(u64) * h.size(), hipMemcpyDeviceToHost));
+  double sum[12] = {0};
+  int per_xcd[8] = {0};
+  for (int w = 0; w < grid; ++w) {
+    for (int k = 0; k < 10; ++k) sum[k] += (double)h[12 * w + k];
+    per_xcd[h[12 * w + 10] & 7] += 1;
+  }
+  const double us = 0.01 / grid;  // 100 MHz ticks -> microseconds, mean per workgroup
+  fprintf(stderr, "[newton persistent] grid %d  per workgroup: items %.1f (products %.1f, stolen %.1f, "
+          "empty sweeps %.1f)  pop %.0f us  acquire %.0f us  K-loops %.0f us  epilogues+other bodies "
+          "%.0f us  drain %.0f us  completion %.0f us  | workgroups per XCC id: %d %d %d %d %d %d %d %d\n",
+          grid, sum[6] / grid, sum[7] / grid, sum[8] / grid, sum[9] / grid, sum[0] * us, sum[1] * us,
+          sum[2] * us, sum[3] * us, sum[4] * us, sum[5] * us, per_xcd[0], per_xcd[1], per_xcd[2],
+          per_xcd[3], per_xcd[4], per_xcd[5], per_xcd[6], per_xcd[7]);
+  return 0;
+}
+
+// Persistent dataflow execution: one launch, no host round trip.
+int run_persistent(NewtonCall& c) {
+  const Plan& pl = c.pl;
+  const WsLayout& lo = c.lo;
+  hipStream_t st = c.st;
+  ProfRun& prof = c.prof;
+  const size_t lds = (PSMEM<NBK> + 16) * sizeof(float);
+  const int grid = std::min(persistent_grid(lds, c.any_careful), 4096);
+  const bool dev_prof = c.opt.newton_prof;
+  PArgs pa;
+  pa.blocks = lo.blocks; pa.states = lo.states; pa.ctl = lo.ctl; pa.slots = lo.slots;
+  pa.metrics = c.metrics; pa.qcap = (unsigned)pl.qcap; pa.nblocks = c.batch;
+  pa.nlive = pl.nlive; pa.num_iters = c.num_iters; pa.tol = c.error_tolerance;
+  pa.prof = dev_prof ? lo.prof : nullptr; pa.grid = grid; pa.avg_thr = c.opt.averaged_err_threshold; pa.nq = pl.nq;
+  if (dev_prof) PS_HIP(hipMemsetAsync(lo.prof, 0, sizeof(u64) * 12 * 4096, st));
+  if (pl.nlive > 0) {
+    prof.begin(2);
+    // every polled word (heads, tails, counters, slot tags) is zeroed before EVERY launch
+    PS_HIP(hipMemsetAsync(lo.ctl, 0, sizeof(PControl), st));
+    PS_HIP(hipMemsetAsync(lo.slots, 0, sizeof(u64) * NQ * pl.qcap, st));
+    hipLaunchKernelGGL(newton_seed_kernel, dim3((c.batch + 63) / 64), dim3(64), 0, st, pa);
+    prof.end();
+    PS_LAUNCH_CHECK();
+    prof.begin(0);
+    hipLaunchKernelGGL((c.any_careful ? newton_persistent_kernel<NBK, true> : newton_persistent_kernel<NBK, false>),
+                       dim3(grid), dim3(256), lds, st, pa);
+    prof.end();
+    PS_LAUNCH_CHECK();
+  }
+  prof.begin(2);
+  hipLaunchKernelGGL(newton_persist_epilogue_kernel, dim3(c.batch), dim3(256), 0, st, pa);
+  prof.end();
+  PS_LAUNCH_CHECK();
+  prof.finish();
+  if (dev_prof && pl.nlive > 0) PS_RC(report_persistent_profile(c, grid));
+  return 0;
+}
+
+// ---- staged execution: which product kernel --------------------------------------------------
+using StageKernel = void (*)(const NewtonBlock*, NewtonState*, const TileEntry*, int, int,
+                             unsigned long long*, unsigned, unsigned);
+// The instantiations of newton_stage_kernel, one row each: the first row that matches the call decides (ANY
+// matches every value), and every row gets its dynamic LDS limit.  Default: the explicitly software-pipelined
+// K loop (gemm_core.hip.h deep_run_pipe); then segmented accumulation, bf16-split arithmetic, developer variants.
+constexpr int ANY = -1;
+struct StageVariant {
+  int xmode, careful, pipe, trace;   // products (0 | 6 | 3), segmented blocks, PS_NEWTON_PIPE, PS_NEWTON_TRACE
+  StageKernel fn;
+};
+const StageVariant STAGE_VARIANTS[] = {
+    // no segmented traced instantiation: a traced call accumulates in chains
+    {0, ANY, 1, 1, newton_stage_kernel<0, true, true>},
+    {0, 1, 1, 0, newton_stage_kernel<0, false, true, true>},
+    {0, 0, 1, 0, newton_stage_kernel<0, false, true>},
+    // (one traced kernel for everything else: float32 products whatever the call's arithmetic)
+    {ANY, ANY, ANY, 1, newton_stage_kernel<0, true>},
+    {6, ANY, ANY, 0, newton_stage_kernel<6>},
+    {3, ANY, ANY, 0, newton_stage_kernel<3>},
+    // no segmented instantiation of the compiler-scheduled K loop: PS_NEWTON_PIPE=0 accumulates in chains
+    {0, ANY, 0, 0, newton_stage_kernel<0>},
+};
+
+StageKernel select_stage_kernel(int xmode, bool careful, bool pipe, bool trace) {
+  static std::once_flag attr_once;   // kernel attributes are per process (one device per process)
+  std::call_once(attr_once, [] {
+    const int lds = (int)(SmemCfg<STAGE_BK>::TOTAL * sizeof(float));
+    for (const StageVariant& v : STAGE_VARIANTS)
+      (void)hipFuncSetAttribute((const void*)v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  });
+  auto match = [](int want, int have) { return want == ANY || want == have; };
+  for (const StageVariant& v : STAGE_VARIANTS)
+    if (match(v.xmode, xmode) && match(v.careful, careful) && match(v.pipe, pipe) && match(v.trace, trace))
+      return v.fn;
+  return nullptr;
+}
+
+// dev trace of the product kernel (PS_NEWTON_TRACE=<file>: records appended per call); one buffer per process
+struct StageTrace {
+  static constexpr unsigned CAP = 1u << 20;
+  unsigned long long* buf = nullptr;   // 8 words of header (word 0: records written), then 8 per record
+  unsigned seq = 0;                    // launch sequence number, across calls
+  // the cleared buffer if the call traces (and the buffer could be allocated), else NULL
+  unsigned long long* begin(const char* path, hipStream_t st) {
+    if (!path) return nullptr;
+    if (!buf && hipMalloc(&buf, (8 + 8 * (size_t)CAP) * sizeof(unsigned long long)) != hipSuccess)
+      buf = nullptr;
+    if (buf) (void)hipMemsetAsync(buf, 0, 64, st);
+    return buf;
+  }
+  // waits for the stream and appends this call's records to the file
+  int dump(const char* path, hipStream_t st) {
+    PS_HIP(hipStreamSynchronize(st));
+    unsigned long long head[8];
+    PS_HIP(hipMemcpy(head, buf, sizeof(head), hipMemcpyDeviceToHost));
+    const size_t nrec = std::min<size_t>((unsigned)head[0], CAP);
+    std::vector<unsigned long long> rec(8 * nrec);
+    if (nrec) PS_HIP(hipMemcpy(rec.data(), buf + 8, rec.size() * 8, hipMemcpyDeviceToHost));
+    if (FILE* f = fopen(path, "ab")) { fwrite(rec.data(), 8, rec.size(), f); fclose(f); }
+    return 0;
+  }
+} g_stage_trace;
+
+// ---- stream groups -----------------------------------------------------------------------
+// The blocks are dealt to G groups (make_plan); every group runs the reference's loop for its
+// blocks -- the same launches, tile for tile, as the single-stream execution -- on a stream of
+// its own: group 0 on the caller's, the others on side streams forked behind the power iteration
+// and joined in front of the copy-out.  A stage launch depends on the previous one of ITS group
+// only, so while one group's launch drains (the last, partly filled round of 512 resident
+// workgroups; the burst of epilogue stores; the first HBM round trip of the next launch) the
+// other group's tiles keep the CUs busy.  Per-block arithmetic, and therefore every bit of the
+// result, does not depend on G.  One host event wait per group and step, one step behind the GPU.
+struct StageGroups {
+  struct Group {
+    hipStream_t st = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr}, join = nullptr;   // ev: end of the even / odd steps
+    bool need_init = true, done = false;
+    int steps = 0, nblk = 0, ninit = 0;
+    const int* ids = nullptr; const TileEntry* init_tiles = nullptr; HostStatus* ring = nullptr;
+  };
+  Group grp[MAX_GROUPS];
+  int G = 0;
+  hipStream_t caller_st = nullptr;
+  hipEvent_t fork_ev = nullptr;   // G > 1
+
+  StageGroups() = default;
+  StageGroups(const StageGroups&) = delete;   // owns the events
+  ~StageGroups() {
+    for (Group& gr : grp) {
+      for (hipEvent_t e : gr.ev) if (e) (void)hipEventDestroy(e);
+      if (gr.join) (void)hipEventDestroy(gr.join);
+    }
+    if (fork_ev) (void)hipEventDestroy(fork_ev);
+  }
+  int init(const NewtonCall& c, HostStatus* status) {
+    const Plan& pl = c.pl;
+    G = pl.ngroups; caller_st = c.st;
+    int off = 0;
+    for (int q = 0; q < G; ++q) {
+      Group& gr = grp[q];
+      gr.st = q == 0 ? caller_st : psh::side_stream(q - 1);   // (the caller's stream may be the null stream)
+      if (q > 0 && !gr.st) return PS_EINTERNAL;
+      gr.nblk = (int)pl.gids[q].size();
+      gr.ids = c.lo.group_ids + off;
+      off += gr.nblk;
+      gr.ninit = pl.ioff[q + 1] - pl.ioff[q];
+      gr.init_tiles = c.lo.init_tiles + pl.ioff[q];
+      gr.ring = status + 64 * q;
+      for (int k = 0; k < 2; ++k) PS_HIP(hipEventCreateWithFlags(&gr.ev[k], hipEventDisableTiming));
+      if (q > 0) PS_HIP(hipEventCreateWithFlags(&gr.join, hipEventDisableTiming));
+    }
+    if (G > 1) PS_HIP(hipEventCreateWithFlags(&fork_ev, hipEventDisableTiming));
+    return 0;
+  }
+  // the side streams start behind everything queued on the caller's stream so far
+  int fork() {
+    if (G == 1) return 0;
+    PS_HIP(hipEventRecord(fork_ev, caller_st));
+    for (int q = 1; q < G; ++q) PS_HIP(hipStreamWaitEvent(grp[q].st, fork_ev, 0));
+    return 0;
+  }
+  // whatever is queued next on the caller's stream runs behind every group
+  int join() {
+    for (int q = 1; q < G; ++q) {
+      PS_HIP(hipEventRecord(grp[q].join, grp[q].st));
+      PS_HIP(hipStreamWaitEvent(caller_st, grp[q].join, 0));
+    }
+    return 0;
+  }
+};
+
+// Staged execution: the step loop of every stream group, the host one step behind the GPU, then the
+// copy-out.  *executed: the largest number of steps a group enqueued.
+int run_staged(NewtonCall& c, int* executed) {
+  Plan& pl = c.pl;
+  const WsLayout& lo = c.lo;
+  const psh::Options& opt = c.opt;
+  ProfRun& prof = c.prof;
+  hipStream_t st = c.st;
+  HostStatus* status = pinned_status();
+  if (!status) return PS_EINTERNAL;
+  unsigned long long* const trace = g_stage_trace.begin(opt.newton_trace, st);
+  const float avg_thr = opt.averaged_err_threshold;
+  const int xmode = opt.products == PS_PRODUCTS_BF16X6 ? 6 : (opt.products == PS_PRODUCTS_BF16X3 ? 3 : 0);
+  const StageKernel newton_stage_kernel_fn = select_stage_kernel(xmode, c.any_careful, opt.pipe != 0, trace != nullptr);
+  if (!newton_stage_kernel_fn) return PS_EINTERNAL;
+  if (!pl.init_tiles.empty()) {
+    StageGroups sg;
+    PS_RC(sg.init(c, status));
+    PS_RC(sg.fork());
+    const int G = sg.G;
+    const int cap = 6 * (c.num_iters + 2) + 4;
+    bool pi_retried = false;
+    for (int g = 0; g < cap; ++g) {
+      // every live group: a try's (re)initialisation if due, the stage launches, the loop control, the step's event
+      for (int q = 0; q < G; ++q) {
+        StageGroups::Group& gr = sg.grp[q];
+        if (gr.done) continue;
+        HostStatus* slot = &gr.ring[g % 64];
+        slot->gen = -1;
+        if (gr.need_init) {
+          prof.begin(2, 1, gr.st);
+          hipLaunchKernelGGL(newton_init1_kernel, dim3(gr.ninit), dim3(256), 0, gr.st, lo.blocks, lo.states, gr.init_tiles);
+          hipLaunchKernelGGL(newton_init2_kernel, dim3(gr.ninit), dim3(256), 0, gr.st, lo.blocks, lo.states, gr.init_tiles);
+          hipLaunchKernelGGL(newton_control_kernel, dim3(1), dim3(256), 0, gr.st, lo.states,
+                             gr.nblk, 0, c.num_iters, c.error_tolerance, g, (HostStatus*)nullptr, avg_thr, gr.ids);
+          prof.end(gr.st);
+          gr.need_init = false;   // until the loop control asks for the next try
+        }
+        prof.begin(0, pl.nstages, gr.st);
+        for (int s = 0; s < pl.nstages; ++s) {
+          const int nt = pl.goff[s][q + 1] - pl.goff[s][q];
+          if (nt == 0) continue;
+          const TileEntry* tl = lo.tiles[s] + pl.goff[s][q];
+          // dev A/B: PS_NEWTON_GRID=g caps the launch at g workgroups that loop over the tile list (0: one per tile)
+          const dim3 grid(c.opt.grid_cap > 0 ? std::min(c.opt.grid_cap, nt) : nt);
+          const size_t lds = SmemCfg<STAGE_BK>::TOTAL * sizeof(float);
+          hipLaunchKernelGGL((newton_stage_kernel_fn), grid, dim3(256), lds, gr.st, lo.blocks, lo.states, tl, nt,
+                             c.stagger, trace, trace ? g_stage_trace.seq++ : 0u, trace ? StageTrace::CAP : 0u);
+        }
+        prof.end(gr.st);
+        hipLaunchKernelGGL(newton_control_kernel, dim3(1), dim3(256), 0, gr.st, lo.states,
+                           gr.nblk, 1, c.num_iters, c.error_tolerance, g, slot, avg_thr, gr.ids);
+        PS_LAUNCH_CHECK();
+        PS_HIP(hipEventRecord(gr.ev[g & 1], gr.st));
+        ++gr.steps;
+      }
+      if (g == 0) continue;   // the host reads a step's status one step later
+      bool restart = false;
+      for (int q = 0; q < G; ++q) {
+        StageGroups::Group& gr = sg.grp[q];
+        if (gr.done) continue;
+        PS_HIP(hipEventSynchronize(gr.ev[(g - 1) & 1]));
+        const HostStatus seen = gr.ring[(g - 1) % 64];
+        if (seen.gen != g - 1) return PS_EINTERNAL;
+        if (g == 1 && !pi_retried && PiPlan::expired_total() != c.pi_expired_before) { restart = true; break; }
+        if (seen.not_done == 0) gr.done = true;
+        gr.need_init = seen.need_init > 0;
+      }
+      if (restart) {
+        pi_retried = true;
+        // The resident power iteration gave up on a team mate that never became resident
+        // (CUs held by another stream's kernels): its blocks carry a NaN eigenvalue.  The
+        // process is on the streaming execution from now on (PiPlan::resident_enabled);
+        // queue the whole call again behind what is already queued and start over.
+        PS_RC(sg.join());   // the front runs on the caller's stream
+        pl.pip.allow_resident = false;
+        PS_RC(enqueue_front(c));
+        PS_RC(sg.fork());
+        for (int q = 0; q < G; ++q) { sg.grp[q].need_init = true; sg.grp[q].done = false; sg.grp[q].steps = 0; }
+        g = -1;
+        continue;
+      }
+      bool all_done = true;
+      for (int q = 0; q < G; ++q) all_done &= sg.grp[q].done;
+      if (all_done) break;
+    }
+    PS_RC(sg.join());   // the copy-out runs behind every group
+    for (int q = 0; q < G; ++q) *executed = std::max(*executed, sg.grp[q].steps);
+  }
+  prof.begin(2);
+  hipLaunchKernelGGL(newton_final_kernel, dim3(c.batch, 32), dim3(256), 0, st, lo.blocks, lo.states, c.metrics);
+  prof.end();
+  PS_LAUNCH_CHECK();
+  prof.finish();
+  if (trace) PS_RC(g_stage_trace.dump(opt.newton_trace, st));
+  return 0;
 }
 
 }  // namespace
 
 extern "C" int ps_newton_averaged_steps(void) { return psh::resolve(nullptr).averaged_steps; }
 
-extern "C" size_t ps_newton_root_workspace_bytes(int batch, const int32_t* n,
-                                                 const int32_t* p,
+extern "C" size_t ps_newton_root_workspace_bytes(int batch, const int32_t* n, const int32_t* p,
                                                  const int32_t* padding_start) {
   if (batch <= 0 || !n || !p) return 0;
   Plan pl;
@@ -1572,414 +1977,17 @@ static int newton_driver(
   bool bad_options = false;
   const psh::Options opt = psh::resolve(options, &bad_options);
   if (bad_options) return PS_EINVAL;
-  if (batch <= 0 || !a || !n || !lda || !p || !out || !ldo || !metrics || !workspace ||
-      num_iters < 1 || symmetry < PS_SYMMETRY_VERIFY || symmetry > PS_SYMMETRY_GENERAL)
-    return PS_EINVAL;
-  if (batch > 65535) return PS_EUNSUPPORTED;  // 16-bit block field of a queue item
-  for (int b = 0; b < batch; ++b)
-    if (n[b] < 1 || lda[b] < n[b] || ldo[b] < n[b] || !a[b] || !out[b]) return PS_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  const bool staged = opt.execution != PS_EXEC_PERSISTENT;
-  if (opt.force_general) symmetry = PS_SYMMETRY_GENERAL;   // dev
-  // Leading steps of every try whose M update is computed in full and averaged with its
-  // transpose (TileFlags above); per block 0 when the caller's hint marks it well conditioned.
-  const int navg = opt.averaged_steps;
-  const float avg_thr = opt.averaged_err_threshold;
-  const int seg_on = (opt.accumulation == PS_ACCUM_SEGMENTED && opt.products == PS_PRODUCTS_F32) ? 1 : 0;
-  Plan pl;
-  // Stream groups of the staged execution (see the product loop below): 2 by default when the call has
-  // work for them (PS_NEWTON_GROUPS / psh::Options::newton_groups: 1 = the single-stream execution).
-  // Measured (tools/dev_stage_variants.py groups, profiles/r06_newton_stream_groups.txt): calls whose
-  // blocks differ in size or exponent (a ViT-B tree: 139.6 -> 133.9 ms with 2 groups, 135-136 with 3 / 4)
-  // gain; homogeneous batches do not (256 x 512^2: 16.1 vs 16.2-16.3 ms, 64 x 1024^2: 23.5 vs 23.7 -- their
-  // launches are whole rounds of equal tiles and the second stream only costs L2 locality), so the default
-  // is 2 groups for mixed calls and 1 otherwise.
-  int want_groups = opt.newton_groups;
-  if (want_groups <= 0) {
-    want_groups = 1;
-    int n0 = -1, p0 = -1;
-    for (int b = 0; b < batch; ++b) {
-      int ne = n[b];
-      if (padding_start) ne = std::max(0, std::min(ne, (int)padding_start[b]));
-      if (ne < 1) continue;
-      const int np_ = psh::round_up(ne, TILE);
-      if (n0 < 0) { n0 = np_; p0 = p[b]; }
-      else if (np_ != n0 || p[b] != p0) { want_groups = 2; break; }
-    }
-  }
-  if (!staged || opt.newton_trace) want_groups = 1;
-  make_plan(pl, batch, n, p, padding_start, staged, want_groups, opt.iters_hint, opt.iters_hint_stride);
-  if (!pl.ok) return PS_EUNSUPPORTED;
-  if (pl.max_n > 16384) return PS_EUNSUPPORTED;
-  // De-phasing of co-resident workgroups (newton_stage_kernel): measured 64 x 1024^2: 21.6 -> 20.9 ms
-  // (-2 ... -5 % by box), no effect at 512^2 (a tile is too short for the delay to pay) or on the
-  // mixed tile lengths of a ViT-B launch: on by itself only when every tile of the call has K >= 1024.
-  int min_npad = 1 << 30;
-  for (int b = 0; b < batch; ++b)
-    if (!pl.chains[b].empty()) min_npad = std::min(min_npad, pl.npad[b]);
-  const int stagger = opt.stagger >= 0 ? opt.stagger : (min_npad >= 1024 && min_npad < (1 << 30) ? ((2 << 16) | 25) : 0);
-  pl.pip.set_options(opt);
-  Arena ar(workspace, workspace_bytes);
-  WsLayout lo;
-  carve(pl, ar, &lo, staged);
-  if (ar.overflow) return PS_EWORKSPACE;
-
-  // ---- upload plan (pinned staging ring: no stream synchronisation) ------------------
-  std::vector<NewtonBlock> hb(batch);
-  std::vector<NewtonState> hs(batch);
-  bool any_careful = false, any_avg = false;
-  for (int b = 0; b < batch; ++b) {
-    NewtonBlock& nb = hb[b];
-    NewtonState& ns = hs[b];
-    memset(&nb, 0, sizeof(nb));
-    memset(&ns, 0, sizeof(ns));
-    nb.a = a[b]; nb.out = out[b];
-    nb.M[0] = lo.mat[0][b]; nb.M[1] = lo.mat[1][b];
-    nb.H[0] = lo.mat[2][b]; nb.H[1] = lo.mat[3][b];
-    nb.Mi = lo.mat[4][b];
-    for (int k = 0; k < NTEMP; ++k) nb.T[k] = lo.mat[5 + k][b];
-    nb.sumsq_partial = lo.sumsq[b];
-    nb.n = pl.n_eff[b]; nb.n_full = n[b]; nb.lda = lda[b]; nb.ldo = ldo[b];
-    nb.npad = pl.npad[b]; nb.p = p[b];
-    nb.alpha = (float)(-1.0 / p[b]);        // DS:774 (float32 of the exact quotient)
-    nb.one_minus_alpha = 1.0f - nb.alpha;   // DS:844, float32 subtraction
-    nb.inv_p = (float)(1.0 / p[b]);
-    nb.nprod = (int)pl.chains[b].size();
-    nb.queue = pl.queue_of[b];
-    for (size_t k = 0; k < pl.chains[b].size(); ++k) {
-      nb.pa[k] = (short)pl.chains[b][k].a;
-      nb.pb[k] = (short)pl.chains[b][k].b;
-      nb.pc[k] = (short)pl.chains[b][k].c;
-    }
-    ns.phase = pl.n_eff[b] >= 1 ? PH_INIT : PH_DONE;
-    ns.ratio = 1.f;
-    // A block whose hint (its Newton iteration count at the previous recompute) lies in
-    // [1, fast_max_iters] is well conditioned: mirrored M updates are exact to 1e-6 there.  Every
-    // other block (no hint, NaN, a slow block) averages the M update of its first steps.
-    const float hv = opt.iters_hint ? opt.iters_hint[(size_t)b * opt.iters_hint_stride] : 0.f;
-    const bool fast = hv >= 1.f && hv <= (float)opt.fast_max_iters;   // false for NaN
-    ns.navg = fast ? 0 : navg;
-    // the accumulation mode is the call's, not the block's: a block's arithmetic does not depend
-    // on its hint beyond the averaged steps
-    ns.seg = seg_on;
-    if (pl.n_eff[b] >= 1) { any_careful |= ns.seg != 0; any_avg |= ns.navg > 0; }
-  }
-  ProfRun prof(st);
-  // Everything from the descriptor upload to the seeded loop state; run again (on the streaming
-  // power iteration) if the resident power iteration reports an expired wait.
-  const unsigned pi_expired_before = PiPlan::expired_total();
-  auto enqueue_front = [&]() -> int {
-    PS_RC(pl.pip.upload(st, a, lda));  // also fixes pl.pip.d_asym
-    for (int b = 0; b < batch; ++b) hb[b].asym = pl.pip.d_asym + b;
-    PS_RC(psh::upload_async(st, lo.blocks, hb.data(), sizeof(NewtonBlock) * batch));
-    PS_RC(psh::upload_async(st, lo.states, hs.data(), sizeof(NewtonState) * batch));
-    PS_RC(pl.pip.enqueue_symmetry(st, symmetry));
-    // ---- power iteration -> ridge epsilon --------------------------------------
-    prof.begin(1);
-    if (relative_matrix_epsilon && !max_ev_given) {
-      int rc = pl.pip.enqueue(st, 100, 1e-6f);  // DS:820-825
-      if (rc) return rc;
-    }
-    prof.end();
-    hipLaunchKernelGGL(newton_setup_kernel, dim3((batch + 255) / 256), dim3(256), 0, st,
-                       lo.states, pl.pip.d_blocks, batch, ridge_epsilon,
-                       relative_matrix_epsilon, max_ev_given);
-    PS_LAUNCH_CHECK();
-    return 0;
-  };
-  if (staged) {
-    for (int s = 0; s < pl.nstages; ++s) {
-      PS_RC(psh::upload_async(st, lo.tiles[s], pl.stage_tiles[s].data(),
-                              sizeof(TileEntry) * pl.stage_tiles[s].size()));
-      if (any_avg && opt.avg_lpt)
-        PS_RC(psh::upload_async(st, lo.tiles_avg[s], pl.stage_tiles_avg[s].data(),
-                                sizeof(TileEntry) * pl.stage_tiles_avg[s].size()));
-    }
-    PS_RC(psh::upload_async(st, lo.init_tiles, pl.init_tiles.data(),
-                            sizeof(TileEntry) * pl.init_tiles.size()));
-    std::vector<int> ids;
-    for (auto& v : pl.gids) ids.insert(ids.end(), v.begin(), v.end());
-    PS_RC(psh::upload_async(st, lo.group_ids, ids.data(), sizeof(int) * ids.size()));
-  }
-  PS_RC(enqueue_front());
-
-  if (!staged) {
-    // ---- persistent dataflow execution: one launch, no host round trip ------------
-    PArgs pa;
-    pa.blocks = lo.blocks; pa.states = lo.states; pa.ctl = lo.ctl; pa.slots = lo.slots;
-    pa.metrics = metrics; pa.qcap = (unsigned)pl.qcap; pa.nblocks = batch;
-    pa.nlive = pl.nlive; pa.num_iters = num_iters; pa.tol = error_tolerance;
-    const size_t lds = (PSMEM<NBK> + 16) * sizeof(float);
-    const bool deep = opt.persistent_deep != 0;
-    const int grid = std::min(persistent_grid(lds, deep || any_careful, opt.wg_per_cu), 4096);
-    const bool dev_prof = opt.newton_prof;
-    pa.prof = dev_prof ? lo.prof : nullptr;
-    pa.grid = grid;
-    pa.avg_thr = avg_thr;
-    pa.nq = pl.nq;
-    if (dev_prof) PS_HIP(hipMemsetAsync(lo.prof, 0, sizeof(u64) * 12 * 4096, st));
-    if (pl.nlive > 0) {
-      prof.begin(2);
-      // every polled word (heads, tails, counters, slot tags) is zeroed before EVERY launch
-      PS_HIP(hipMemsetAsync(lo.ctl, 0, sizeof(PControl), st));
-      PS_HIP(hipMemsetAsync(lo.slots, 0, sizeof(u64) * NQ * pl.qcap, st));
-      hipLaunchKernelGGL(newton_seed_kernel, dim3((batch + 63) / 64), dim3(64), 0, st, pa);
-      prof.end();
-      PS_LAUNCH_CHECK();
-      prof.begin(0);
-      if (any_careful)
-        hipLaunchKernelGGL((newton_persistent_kernel<NBK, false, true>), dim3(grid), dim3(256), lds, st, pa);
-      else if (deep)
-        hipLaunchKernelGGL((newton_persistent_kernel<NBK, true>), dim3(grid), dim3(256), lds, st, pa);
-      else
-        hipLaunchKernelGGL((newton_persistent_kernel<NBK, false>), dim3(grid), dim3(256), lds, st, pa);
-      prof.end();
-      PS_LAUNCH_CHECK();
-    }
-    prof.begin(2);
-    hipLaunchKernelGGL(newton_persist_epilogue_kernel, dim3(batch), dim3(256), 0, st, pa);
-    prof.end();
-    PS_LAUNCH_CHECK();
-    prof.finish();
-    if (dev_prof && pl.nlive > 0) {  // dev only: per-workgroup time split of the persistent kernel
-      std::vector<u64> h(12 * (size_t)grid);
-      PS_HIP(hipStreamSynchronize(st));
-      PS_HIP(hipMemcpy(h.data(), lo.prof, sizeof(u64) * h.size(), hipMemcpyDeviceToHost));
-      double sum[12] = {0};
-      int per_xcd[8] = {0};
-      for (int w = 0; w < grid; ++w) {
-        for (int k = 0; k < 10; ++k) sum[k] += (double)h[12 * w + k];
-        per_xcd[h[12 * w + 10] & 7] += 1;
-      }
-      const double us = 0.01 / grid;  // 100 MHz ticks -> microseconds, mean per workgroup
-      fprintf(stderr, "[newton persistent] grid %d  per workgroup: items %.1f (products %.1f, stolen %.1f, "
-              "empty sweeps %.1f)  pop %.0f us  acquire %.0f us  K-loops %.0f us  epilogues+other bodies "
-              "%.0f us  drain %.0f us  completion %.0f us  | workgroups per XCC id: %d %d %d %d %d %d %d %d\n",
-              grid, sum[6] / grid, sum[7] / grid, sum[8] / grid, sum[9] / grid, sum[0] * us, sum[1] * us,
-              sum[2] * us, sum[3] * us, sum[4] * us, sum[5] * us, per_xcd[0], per_xcd[1], per_xcd[2],
-              per_xcd[3], per_xcd[4], per_xcd[5], per_xcd[6], per_xcd[7]);
-    }
-    if (iters_executed_host) *iters_executed_host = -1;
-    return PS_OK;
-  }
-
-  // ---- staged execution --------------------------------------------------------------
-  HostStatus* status = pinned_status();
-  if (!status) return PS_EINTERNAL;
-  // Variant of the product kernel.  Default: BK = 32, two register sets of global loads, the
-  // explicitly software-pipelined K loop (gemm_core.hip.h deep_run_pipe), 2 workgroups per CU;
-  // the other instantiations are developer A/B variants (psh::Options::stage_bk / stage_deep /
-  // pipe).  The bf16-split arithmetic has its own instantiations.
-  const int stage_bk = opt.stage_bk, stage_deep = opt.stage_deep;
-  const int xmode = opt.products == PS_PRODUCTS_BF16X6 ? 6 : (opt.products == PS_PRODUCTS_BF16X3 ? 3 : 0);
-  const bool pipe_mode = opt.pipe != 0 && stage_bk == 32 && stage_deep;
-  {
-    static std::once_flag attr_once;   // kernel attributes are per process (one device per process)
-    std::call_once(attr_once, [] {
-      const int lds = (int)(SmemCfg<32>::TOTAL * sizeof(float));
-      const void* fns[] = {(const void*)newton_stage_kernel<32, false>,
-                           (const void*)newton_stage_kernel<32, true>,
-                           (const void*)newton_stage_kernel<32, true, 6>,
-                           (const void*)newton_stage_kernel<32, true, 3>,
-                           (const void*)newton_stage_kernel<32, true, 0, false, true>,
-                           (const void*)newton_stage_kernel<32, true, 0, false, true, true>,
-                           (const void*)newton_stage_kernel<32, true, 0, true, true>,
-                           (const void*)newton_stage_kernel<32, true, 0, true>};
-      for (const void* f : fns)
-        (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    });
-  }
-  // dev trace of the product kernel (PS_NEWTON_TRACE=<file>: records appended per call)
-  constexpr unsigned TRACE_CAP = 1u << 20;
-  static unsigned long long* trace_buf = nullptr;
-  static unsigned trace_seq = 0;
-  const char* trace_path = opt.newton_trace;
-  if (trace_path && !trace_buf) {
-    if (hipMalloc(&trace_buf, (8 + 8 * (size_t)TRACE_CAP) * sizeof(unsigned long long)) != hipSuccess)
-      trace_buf = nullptr;
-  }
-  if (!trace_path) { /* tracing off for this call */ }
-  unsigned long long* const trace_on = trace_path ? trace_buf : nullptr;
-  if (trace_on) (void)hipMemsetAsync(trace_on, 0, 64, st);
-  const int ninit = (int)pl.init_tiles.size();
-  int executed = 0;
-  if (ninit > 0) {
-    // ---- stream groups -----------------------------------------------------------------------
-    // The blocks are dealt to G groups (make_plan); every group runs the reference's loop for its
-    // blocks -- the same launches, tile for tile, as the single-stream execution -- on a stream of
-    // its own: group 0 on the caller's, the others on side streams forked behind the power iteration
-    // and joined in front of the copy-out.  A stage launch depends on the previous one of ITS group
-    // only, so while one group's launch drains (the last, partly filled round of 512 resident
-    // workgroups; the burst of epilogue stores; the first HBM round trip of the next launch) the
-    // other group's tiles keep the CUs busy.  Per-block arithmetic, and therefore every bit of the
-    // result, does not depend on G.  One host event wait per group and step, one step behind the GPU.
-    const int G = pl.ngroups;
-    struct Grp {
-      hipStream_t st = nullptr;
-      hipEvent_t ev[2] = {nullptr, nullptr};
-      hipEvent_t join = nullptr;
-      bool need_init = true, done = false;
-      int since_init = 0, steps = 0, nblk = 0, ninit = 0;
-      const int* ids = nullptr;
-      const TileEntry* init_tiles = nullptr;
-      HostStatus* ring = nullptr;
-    };
-    Grp grp[MAX_GROUPS];
-    hipEvent_t fork_ev = nullptr;
-    int rc = 0;
-    auto cleanup = [&]() {
-      for (int q = 0; q < G; ++q) {
-        for (int k = 0; k < 2; ++k) if (grp[q].ev[k]) (void)hipEventDestroy(grp[q].ev[k]);
-        if (grp[q].join) (void)hipEventDestroy(grp[q].join);
-      }
-      if (fork_ev) (void)hipEventDestroy(fork_ev);
-    };
-    {
-      int off = 0;
-      for (int q = 0; q < G && !rc; ++q) {
-        Grp& gr = grp[q];
-        gr.st = q == 0 ? st : side_stream(q - 1);   // (the caller's stream may be the null stream)
-        if (q > 0 && !gr.st) { rc = PS_EINTERNAL; break; }
-        gr.nblk = (int)pl.gids[q].size();
-        gr.ids = lo.group_ids + off;
-        off += gr.nblk;
-        gr.ninit = pl.ioff[q + 1] - pl.ioff[q];
-        gr.init_tiles = lo.init_tiles + pl.ioff[q];
-        gr.ring = status + 64 * q;
-        for (int k = 0; k < 2 && !rc; ++k) rc = (int)hipEventCreateWithFlags(&gr.ev[k], hipEventDisableTiming);
-        if (!rc && q > 0) rc = (int)hipEventCreateWithFlags(&gr.join, hipEventDisableTiming);
-      }
-      if (!rc && G > 1) rc = (int)hipEventCreateWithFlags(&fork_ev, hipEventDisableTiming);
-    }
-    auto fork = [&]() -> int {   // the side streams start behind everything queued on st so far
-      if (G == 1) return 0;
-      PS_HIP(hipEventRecord(fork_ev, st));
-      for (int q = 1; q < G; ++q) PS_HIP(hipStreamWaitEvent(grp[q].st, fork_ev, 0));
-      return 0;
-    };
-    if (!rc) rc = fork();
-    const int cap = 6 * (num_iters + 2) + 4;
-    bool pi_retried = false;
-    for (int g = 0; g < cap && !rc; ++g) {
-      for (int q = 0; q < G && !rc; ++q) {
-        Grp& gr = grp[q];
-        if (gr.done) continue;
-        HostStatus* slot = &gr.ring[g % 64];
-        slot->gen = -1;
-        if (gr.need_init) {
-          prof.begin(2, 1, gr.st);
-          hipLaunchKernelGGL(newton_init1_kernel, dim3(gr.ninit), dim3(256), 0, gr.st, lo.blocks,
-                             lo.states, gr.init_tiles);
-          hipLaunchKernelGGL(newton_init2_kernel, dim3(gr.ninit), dim3(256), 0, gr.st, lo.blocks,
-                             lo.states, gr.init_tiles);
-          hipLaunchKernelGGL(newton_control_kernel, dim3(1), dim3(256), 0, gr.st, lo.states,
-                             gr.nblk, 0, num_iters, error_tolerance, g, (HostStatus*)nullptr, avg_thr, gr.ids);
-          prof.end(gr.st);
-          gr.since_init = 0;
-        }
-        const bool avg_order = any_avg && opt.avg_lpt && gr.since_init < navg;
-        ++gr.since_init;
-        prof.begin(0, pl.nstages, gr.st);
-        for (int s = 0; s < pl.nstages; ++s) {
-          const int nt = pl.goff[s][q + 1] - pl.goff[s][q];
-          if (nt == 0) continue;
-          const TileEntry* tl = (avg_order ? lo.tiles_avg[s] : lo.tiles[s]) + pl.goff[s][q];
-          const dim3 grid(stage_grid(nt, opt.grid_cap));
-          const size_t lds = SmemCfg<32>::TOTAL * sizeof(float);
-          hipStream_t gst = gr.st;
-#define PS_STAGE(...)                                                                        \
-  hipLaunchKernelGGL((newton_stage_kernel<__VA_ARGS__>), grid, dim3(256), lds, gst, lo.blocks, \
-                     lo.states, tl, nt, stagger)
-          if (pipe_mode && xmode == 0 && trace_on)
-            hipLaunchKernelGGL((newton_stage_kernel<32, true, 0, true, true>), grid, dim3(256), lds, gst,
-                               lo.blocks, lo.states, tl, nt, navg, trace_on, trace_seq++, TRACE_CAP);
-          else if (pipe_mode && xmode == 0 && any_careful) PS_STAGE(32, true, 0, false, true, true);
-          else if (pipe_mode && xmode == 0) PS_STAGE(32, true, 0, false, true);
-          else if (trace_on)
-            hipLaunchKernelGGL((newton_stage_kernel<32, true, 0, true>), grid, dim3(256), lds, gst,
-                               lo.blocks, lo.states, tl, nt, navg, trace_on, trace_seq++, TRACE_CAP);
-          else if (xmode == 6) PS_STAGE(32, true, 6);
-          else if (xmode == 3) PS_STAGE(32, true, 3);
-          else if (stage_bk == 32 && stage_deep) PS_STAGE(32, true);
-          else if (stage_bk == 32) PS_STAGE(32, false);
-          else if (stage_deep)
-            hipLaunchKernelGGL((newton_stage_kernel<16, true>), grid, dim3(256),
-                               SmemCfg<16>::TOTAL * sizeof(float), gst, lo.blocks, lo.states, tl, nt, navg);
-          else
-            hipLaunchKernelGGL((newton_stage_kernel<16, false>), grid, dim3(256),
-                               SmemCfg<16>::TOTAL * sizeof(float), gst, lo.blocks, lo.states, tl, nt, navg);
-#undef PS_STAGE
-        }
-        prof.end(gr.st);
-        hipLaunchKernelGGL(newton_control_kernel, dim3(1), dim3(256), 0, gr.st, lo.states,
-                           gr.nblk, 1, num_iters, error_tolerance, g, slot, avg_thr, gr.ids);
-        if ((rc = (int)hipGetLastError()) != 0) break;
-        if ((rc = (int)hipEventRecord(gr.ev[g & 1], gr.st)) != 0) break;
-        ++gr.steps;
-      }
-      if (rc) break;
-      if (g == 0) {
-        for (int q = 0; q < G; ++q) grp[q].need_init = false;
-        continue;
-      }
-      bool restart = false;
-      for (int q = 0; q < G && !rc; ++q) {
-        Grp& gr = grp[q];
-        if (gr.done) continue;
-        if ((rc = (int)hipEventSynchronize(gr.ev[(g - 1) & 1])) != 0) break;
-        const HostStatus seen = gr.ring[(g - 1) % 64];
-        if (seen.gen != g - 1) { rc = PS_EINTERNAL; break; }
-        if (g == 1 && !pi_retried && PiPlan::expired_total() != pi_expired_before) { restart = true; break; }
-        if (seen.not_done == 0) gr.done = true;
-        gr.need_init = seen.need_init > 0;
-      }
-      if (rc) break;
-      if (restart) {
-        pi_retried = true;
-        // The resident power iteration gave up on a team mate that never became resident
-        // (CUs held by another stream's kernels): its blocks carry a NaN eigenvalue.  The
-        // process is on the streaming execution from now on (PiPlan::resident_enabled);
-        // queue the whole call again behind what is already queued and start over.
-        for (int q = 1; q < G && !rc; ++q) {   // join the side streams first: the front runs on st
-          if ((rc = (int)hipEventRecord(grp[q].join, grp[q].st)) != 0) break;
-          rc = (int)hipStreamWaitEvent(st, grp[q].join, 0);
-        }
-        if (rc) break;
-        pl.pip.allow_resident = false;
-        if ((rc = enqueue_front()) != 0) break;
-        if ((rc = fork()) != 0) break;
-        for (int q = 0; q < G; ++q) { grp[q].need_init = true; grp[q].done = false; grp[q].steps = 0; }
-        g = -1;
-        continue;
-      }
-      bool all_done = true;
-      for (int q = 0; q < G; ++q) all_done &= grp[q].done;
-      if (all_done) break;
-    }
-    // join: the copy-out (and whatever the caller queues next on st) runs behind every group
-    for (int q = 1; q < G && !rc; ++q) {
-      if ((rc = (int)hipEventRecord(grp[q].join, grp[q].st)) != 0) break;
-      rc = (int)hipStreamWaitEvent(st, grp[q].join, 0);
-    }
-    for (int q = 0; q < G; ++q) executed = std::max(executed, grp[q].steps);
-    cleanup();
-    if (rc) return rc;
-  }
-  prof.begin(2);
-  hipLaunchKernelGGL(newton_final_kernel, dim3(batch, 32), dim3(256), 0, st, lo.blocks,
-                     lo.states, metrics);
-  prof.end();
-  PS_LAUNCH_CHECK();
-  prof.finish();
-  if (trace_on) {   // dev only: waits for the stream and appends this call's records to the file
-    PS_HIP(hipStreamSynchronize(st));
-    unsigned long long head[8];
-    PS_HIP(hipMemcpy(head, trace_on, sizeof(head), hipMemcpyDeviceToHost));
-    const size_t nrec = std::min<size_t>((unsigned)head[0], TRACE_CAP);
-    std::vector<unsigned long long> rec(8 * nrec);
-    if (nrec) PS_HIP(hipMemcpy(rec.data(), trace_on + 8, rec.size() * 8, hipMemcpyDeviceToHost));
-    if (FILE* f = fopen(trace_path, "ab")) { fwrite(rec.data(), 8, rec.size(), f); fclose(f); }
-  }
+  NewtonCall c{(hipStream_t)stream, a, n, lda, p, padding_start, batch, num_iters, ridge_epsilon,
+               error_tolerance, relative_matrix_epsilon, max_ev_given, symmetry, out, ldo, metrics,
+               workspace, workspace_bytes, opt};
+  PS_RC(validate_and_plan(c));
+  fill_descriptors(c);
+  c.prof.start(c.st);
+  if (c.staged) PS_RC(upload_stage_tables(c));
+  PS_RC(enqueue_front(c));
+  int executed = c.staged ? 0 : -1;   // the persistent execution has no host-side count
+  if (c.staged) PS_RC(run_staged(c, &executed));
+  else PS_RC(run_persistent(c));
   if (iters_executed_host) *iters_executed_host = executed;
   return PS_OK;
 }

@@ -27,17 +27,12 @@ struct Options {
   int eigh_td = 1;                 // eigh_solver AUTO / TRIDIAGONAL: eigh_td.hip.h for 129 ... 4096 rows (PS_EIGH_TD)
   // ---- dev (environment, PS_DEV_ENV=1 only) -----------------------------------------------------
   bool force_general = false;      // PS_NEWTON_SYMMETRIC=0: full products for every block
-  int stage_bk = 32;               // PS_NEWTON_BK = 16 | 32
-  int stage_deep = 1;              // PS_NEWTON_DEEP
-  int persistent_deep = 0;         // PS_NEWTON_DEEP (persistent execution)
   int pipe = 1;                    // PS_NEWTON_PIPE
   int grid_cap = 0;                // PS_NEWTON_GRID
   int newton_groups = 0;           // PS_NEWTON_GROUPS: stream groups of the staged execution (0 = default 2; 1 = one stream)
-  int wg_per_cu = 0;               // PS_NEWTON_WG_PER_CU
   bool newton_prof = false;        // PS_NEWTON_PROF
   const char* newton_trace = nullptr;  // PS_NEWTON_TRACE=<file>
   int stagger = -1;                // PS_NEWTON_STAGGER: -1 = auto (25 us when every tile of a launch has K >= 1024), 0 = off, else (mode << 16) | microseconds (dev)
-  int avg_lpt = 0;                 // PS_NEWTON_AVG_LPT: two-pass tiles first in averaged launches (measured: +1 % time)
   int eigh_small = 1;              // PS_EIGH_SMALL
   int eigh_small_refresh = 1;      // PS_EIGH_SMALL_REFRESH
   bool eigh_trace = false;         // PS_EIGH_TRACE

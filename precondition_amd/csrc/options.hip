@@ -32,13 +32,9 @@ void ps_dev_env_overrides(Options& o) {
     o.power_iteration = e[0] == '0' ? PS_PI_STREAMING : PS_PI_AUTO;
   if (const char* e = getenv("PS_PI_TIMEOUT_MS")) o.pi_timeout_ms = atof(e);
   if (const char* e = getenv("PS_NEWTON_SYMMETRIC")) o.force_general = atoi(e) == 0;
-  if (const char* e = getenv("PS_NEWTON_BK")) o.stage_bk = atoi(e) == 16 ? 16 : 32;
-  if (const char* e = getenv("PS_NEWTON_DEEP")) o.stage_deep = o.persistent_deep = atoi(e) != 0;
   geti("PS_NEWTON_PIPE", o.pipe);
   geti("PS_NEWTON_GRID", o.grid_cap);
   geti("PS_NEWTON_GROUPS", o.newton_groups);
-  geti("PS_NEWTON_WG_PER_CU", o.wg_per_cu);
-  geti("PS_NEWTON_AVG_LPT", o.avg_lpt);
   geti("PS_NEWTON_STAGGER", o.stagger);
   o.newton_prof = getenv("PS_NEWTON_PROF") != nullptr;
   o.newton_trace = getenv("PS_NEWTON_TRACE");

@@ -2,7 +2,6 @@
   careful   no hint: 4 averaged steps + segmented accumulation (CAREFUL kernel, 1 workgroup per CU)
   chain     no hint, accumulation = chain (the round-3 default: 2 workgroups per CU)
   hinted    last step's iteration counts as ps_options.iters_hint (fast path where <= 8)
-  + PS_NEWTON_AVG_LPT=0 (dev env) for the tile order of averaged launches.
 Usage: python tools/dev_r4_newton.py [steps]"""
 import os
 import sys
@@ -45,10 +44,6 @@ for name in ("cfg2_256x512_p4", "headline_64x1024_p4"):
   run(w, "careful (no hint)", {}, False)
   run(w, "chain (no hint) = round 3", {"accumulation": "chain"}, False)
   run(w, "hinted (fast)", {}, True)
-  os.environ["PS_NEWTON_AVG_LPT"] = "0"
-  run(w, "chain, avg tiles in list order", {"accumulation": "chain"}, False)
-  run(w, "careful, avg tiles in list order", {}, False)
-  os.environ.pop("PS_NEWTON_AVG_LPT")
   print("  parity (hinted):", bench.parity_sample(w, count=2), flush=True)
   del w
   torch.cuda.empty_cache()

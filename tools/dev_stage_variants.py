@@ -1,5 +1,5 @@
-"""Dev: A/B of the Newton stage-kernel variants (PS_NEWTON_BK / PS_NEWTON_DEEP are read once per
-process, so each variant runs in a child process)."""
+"""Dev: A/B of the Newton stage-kernel variants (PS_NEWTON_PIPE, `groups`: PS_NEWTON_GROUPS, `grid`:
+PS_NEWTON_GRID); each variant runs in a child process of its own."""
 import os; os.environ.setdefault("PS_DEV_ENV", "1")   # developer switches (PS_*) are read only under PS_DEV_ENV=1
 import os, subprocess, sys
 CHILD = r'''
@@ -27,9 +27,7 @@ if "vit" in os.environ.get("PS_DEV_EXTRA", ""):
     torch.cuda.synchronize(); best = min(best, (time.perf_counter()-t0)/2*1e3)
   print("    vit_b %.1f ms" % best, flush=True)
 '''
-combos = [dict(), dict(PS_NEWTON_PIPE="0", PS_NEWTON_BK="16", PS_NEWTON_DEEP="1"), dict(PS_NEWTON_PIPE="0", PS_NEWTON_BK="16", PS_NEWTON_DEEP="0"), dict(), dict(PS_NEWTON_PIPE="0", PS_NEWTON_BK="16", PS_NEWTON_DEEP="1")]
-if len(sys.argv) > 1 and sys.argv[1] == "bk":
-  combos = [dict(PS_NEWTON_BK=bk, PS_NEWTON_DEEP=deep) for bk, deep in (("32", "1"), ("16", "1"), ("16", "0"), ("32", "0"))]
+combos = [dict(), dict(PS_NEWTON_PIPE="0"), dict(), dict(PS_NEWTON_PIPE="0")]
 if len(sys.argv) > 1 and sys.argv[1] == "groups":   # round 6: stream groups of the staged execution (same bits for every count)
   os.environ["PS_DEV_EXTRA"] = "vit"
   combos = [dict(PS_NEWTON_GROUPS=g) for g in ("1", "2", "3", "4", "1", "2")]

@@ -288,7 +288,10 @@ int ps_stats_update_f32(void* stream, const float* g, int64_t rows, int64_t cols
  * be NULL (no padding) or per-block values (rows/cols >= it are treated as zero).
  * out_lambda[b] (device) receives s of the last executed step, out_iters[b]
  * (device, may be NULL) the number of steps executed.  out_v (device, may be
- * NULL) receives the normalised vector, n_max floats per block.  Host arrays:
+ * NULL) receives the normalised vectors, one row of ldv floats per block, ldv >= n_max =
+ * the largest effective size min(n[b], padding_start[b]) of the batch (else PS_EINVAL).  Of
+ * row b only that block's first min(n[b], padding_start[b]) floats are written: everything
+ * behind them, where the reference holds zeros, keeps the caller's values.  Host arrays:
  * a, n, lda, padding_start.  symmetry: PS_SYMMETRY_* (the matrix need not be symmetric). */
 size_t ps_power_iteration_workspace_bytes(int batch, const int32_t* n);
 int ps_power_iteration_batched_f32(void* stream, const float* const* a,

@@ -167,6 +167,69 @@ __device__ __forceinline__ float pi_half_sum(float x) {
 }
 constexpr int PI_SUM_LANE = 16;   // (lane & 31) of the lanes that hold pi_half_sum's total
 
+// pi_half_sum of the 16 rows of a tile pass at once (pi_block_kernel).  pi_half_sum's tree pairs, per
+// row of 16 lanes, lane l with l ^ 8, then ^ 4, ^ 2, ^ 1 (its rotations read lane l - d, whose
+// value equals lane l ^ d's once the earlier steps made the values periodic), then the lower
+// with the upper row.  Both partners of a pairing compute the same sum, so they can share the
+// work: at distance 8 the lanes 0-7 of a row reduce one half of the 16 tile rows and the lanes
+// 8-15 the other, at distance 4 each bank of 4 lanes keeps four of them; same operands, same
+// order of distances, 16 + 8 + 4 + 4 + 2 adds for 16 sums instead of 16 chains of five.  The
+// two halves of a stage are two DPP adds with complementary bank masks writing one register.
+// Inline assembly: the masked add cannot be expressed through update_dpp (a masked-off lane would
+// add `old`), and the hazard recogniser does not look into assembly, so every block pads the
+// 2 wait states between a VALU write and a DPP / permlane read itself.
+__device__ __forceinline__ float pi_bfly8(float a, float b) {   // banks 0,1: a, banks 2,3: b
+  float r;
+  asm volatile("s_nop 1\n\t"
+               "v_add_f32_dpp %0, %1, %1 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+               "v_add_f32_dpp %0, %2, %2 row_ror:8 row_mask:0xf bank_mask:0xc"
+               : "=&v"(r) : "v"(a), "v"(b));
+  return r;
+}
+__device__ __forceinline__ float pi_bfly4(float a, float b) {   // banks 0,2: a, banks 1,3: b
+  float r;
+  asm volatile("s_nop 1\n\t"
+               "v_add_f32_dpp %0, %1, %1 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"   // lane l + 4
+               "v_add_f32_dpp %0, %2, %2 row_shr:4 row_mask:0xf bank_mask:0xa"       // lane l - 4
+               : "=&v"(r) : "v"(a), "v"(b));
+  return r;
+}
+// `tie` is not touched: an operand of the caller's NEXT four dot products, so that they are
+// scheduled behind this block instead of all sixteen ahead of the first (with 192 registers of
+// matrix data beside them that spilled).
+__device__ __forceinline__ float pi_quad_sum(float a, float& tie) {   // lane l ^ 2, then lane l ^ 1
+  float r;
+  asm volatile("s_nop 1\n\t"
+               "v_add_f32_dpp %0, %2, %2 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+               "s_nop 1\n\t"
+               "v_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
+               : "=&v"(r), "+v"(tie) : "v"(a));
+  return r;
+}
+// lower + upper row of each half-wavefront: the lanes of the lower row get a's total, the
+// lanes of the upper row b's (the swap exchanges a's upper rows with b's lower rows).
+__device__ __forceinline__ float pi_rows_sum(float a, float b) {
+  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+  return a + b;
+}
+// The sums of d[it] over the 32 lanes of each half-wavefront, it = 0..15, in pi_half_sum's order,
+// four rows at a time: pi_sum4 takes the dot products of rows it = 4 m .. 4 m + 3 to f[m], the
+// store finishes the four f.  Rows are dealt so that the sums finish in row order: lanes 8-15 of a
+// row of 16 take the odd `it`, banks 1 and 3 the (it & 2) ones, the upper row it & 4, and t23
+// rather than t01 it & 8.  Lane (c4 & 3) < 2 of every bank writes one sum.
+__device__ __forceinline__ float pi_sum4(float d0, float d1, float d2, float d3, float& tie) {
+  return pi_quad_sum(pi_bfly4(pi_bfly8(d0, d1), pi_bfly8(d2, d3)), tie);
+}
+__device__ __forceinline__ void pi_half_sum16_store(const float (&f)[4], float* Pu, int wave,
+                                                    int c4, int rh) {
+  const float t01 = pi_rows_sum(f[0], f[1]);   // m = upper row ? 1 : 0
+  const float t23 = pi_rows_sum(f[2], f[3]);   // m = upper row ? 3 : 2
+  const int j = c4 & 3;
+  const int it = 8 * j + ((c4 >> 2) & 4) + ((c4 >> 1) & 2) + ((c4 >> 3) & 1);
+  const float u = j ? t23 : t01;
+  if (j < 2) Pu[32 * wave + 2 * it + rh] = u;
+}
+
 // Row dot products of one 128x128 tile with a 128-vector: u[r] = sum_c A[r0+r][c0+c] v[c],
 // written to P_out[r].  Register streaming: lane = (row parity rh, float4 column group c4),
 // a wavefront walks 32 rows two at a time with all 16 loads in flight.
@@ -782,18 +845,26 @@ __device__ __forceinline__ void pi_blk_offdiag(const PiBlock* pb, const f32x4 (&
   asm volatile("" : "+v"(c4), "+v"(rh), "+v"(wave));   // see pi_blk_diag
   const int r0 = I * PT, c0 = J * PT;
   const float* vI = vn + r0;
-  const f32x4 vj = *reinterpret_cast<const f32x4*>(vn + c0 + 4 * c4);
+  f32x4 vj = *reinterpret_cast<const f32x4*>(vn + c0 + 4 * c4);
   float* Pu = P + (I * t + J) * PT;
   f32x4 w = {0.f, 0.f, 0.f, 0.f};
+  float f[4];
 #pragma unroll
-  for (int it = 0; it < 16; ++it) {
-    const int r = 32 * wave + 2 * it + rh;
-    const float u = pi_half_sum(pi_dot4(x[it], vj));
-    if (c4 == PI_SUM_LANE) Pu[r] = u;
-    const float vi = vI[r];
+  for (int m = 0; m < 4; ++m) {
+    float dsum[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) w[e] = __fmaf_rn(x[it][e], vi, w[e]);
+    for (int q = 0; q < 4; ++q) {
+      const int it = 4 * m + q, r = 32 * wave + 2 * it + rh;
+      dsum[q] = pi_dot4(x[it], vj);
+      const float vi = vI[r];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) w[e] = __fmaf_rn(x[it][e], vi, w[e]);
+    }
+    float tie = vj[0];
+    f[m] = pi_sum4(dsum[0], dsum[1], dsum[2], dsum[3], tie);
+    vj[0] = tie;
   }
+  pi_half_sum16_store(f, Pu, wave, c4, rh);
   if (asym) {
     // pi_tile_from_regs's rare path: the mirrored tile (J, I) from memory, a few rows at a time
     const f32x4 vi4 = *reinterpret_cast<const f32x4*>(vI + 4 * c4);
@@ -831,7 +902,7 @@ __device__ __forceinline__ void pi_blk_diag(const PiBlock* pb, const float* Dx, 
                                             const float* vn, float* P, const int* rbs, bool asym,
                                             int wave, int c4, int rh) {
   const int o = X * PT;
-  const f32x4 vj = *reinterpret_cast<const f32x4*>(vn + o + 4 * c4);
+  f32x4 vj = *reinterpret_cast<const f32x4*>(vn + o + 4 * c4);
   float* Pu = P + (X * t + X) * PT;
   if (asym) {
     const int n = pb->n, lda = pb->lda;
@@ -870,21 +941,29 @@ __device__ __forceinline__ void pi_blk_diag(const PiBlock* pb, const float* Dx, 
     lo[0][e] = Dx + b + m0;
     lo[1][e] = Dx + b + m1;
   }
+  float f[4];
 #pragma unroll
-  for (int it = 0; it < 16; ++it) {
-    const int h = it >> 1, rot = h & 3;   // rot == R & 3
-    f32x4 xx;
-    if (d >= h) {
-      const f32x4 q = *reinterpret_cast<const f32x4*>(up + rrow[2 * it] - 4 * h);
+  for (int m = 0; m < 4; ++m) {
+    float dsum[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) xx[e] = q[(e + rot) & 3];
-    } else {
+    for (int k = 0; k < 4; ++k) {
+      const int it = 4 * m + k, h = it >> 1, rot = h & 3;   // rot == R & 3
+      f32x4 xx;
+      if (d >= h) {
+        const f32x4 q = *reinterpret_cast<const f32x4*>(up + rrow[2 * it] - 4 * h);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) xx[e] = lo[it & 1][e][4 * h];
+        for (int e = 0; e < 4; ++e) xx[e] = q[(e + rot) & 3];
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) xx[e] = lo[it & 1][e][4 * h];
+      }
+      dsum[k] = pi_dot4(xx, vj);
     }
-    const float u = pi_half_sum(pi_dot4(xx, vj));
-    if (c4 == PI_SUM_LANE) Pu[32 * wave + 2 * it + rh] = u;
+    float tie = vj[0];
+    f[m] = pi_sum4(dsum[0], dsum[1], dsum[2], dsum[3], tie);
+    vj[0] = tie;
   }
+  pi_half_sum16_store(f, Pu, wv, c4v, rhv);
 }
 
 static __global__ __launch_bounds__(512, 1) void pi_block_kernel(PiBlock* blocks, int num_iters,

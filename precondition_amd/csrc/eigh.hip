@@ -34,6 +34,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <mutex>
 #include <vector>
 
 #include "common.h"
@@ -63,7 +64,7 @@ struct EighBlock {
   float* offpart;  // [npairs * rounds] pivot off-norm^2 partials of the current sweep
   float* sumsq_partial;
   float* evals;
-  float* evals_out;  // mode 1 only
+  float* evals_out;  // plain eigenpairs only
   int n, n_full, lda, ldo, npad, nb, npairs, p;
   float alpha, ridge, max_ev, normD;
   int active, sweeps;
@@ -973,9 +974,6 @@ __global__ __launch_bounds__(256) void eigh_rayleigh_f64_kernel(EighBlock* block
 // Tiles: 64 x 64 per workgroup (4 per 128 x 128 entry of the tile list), one wavefront per
 // 32 x 32 quadrant on the float64 MFMA (v_mfma_f64_16x16x4_f64; 2 * 2n^3 flops per matrix).
 // STAGE 0: (X, W) = hi / lo of D V.   STAGE 1: A = V^T (X + W).
-// STAGE 2: X = 1.5 I - 0.5 V^T V (the Newton-Schulz factor of the final polish: with a float32
-// Gram matrix the off-diagonal entries of V^T V carry sqrt(n) eps32 of noise, as large as the
-// loss of orthogonality they are meant to measure).
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 template <int STAGE>
@@ -1031,7 +1029,7 @@ __global__ __launch_bounds__(256) void eigh_reproject_f64_kernel(EighBlock* bloc
       for (int a = 0; a < 2; ++a) af[a] = (double)sL[kk + fk][qr + 16 * a + fi];
 #pragma unroll
       for (int b = 0; b < 2; ++b)
-        bf[b] = STAGE != 1 ? (double)sR[kk + fk][qc + 16 * b + fi]
+        bf[b] = STAGE == 0 ? (double)sR[kk + fk][qc + 16 * b + fi]
                            : (double)sR[kk + fk][qc + 16 * b + fi] +
                                  (double)sR2[kk + fk][qc + 16 * b + fi];
 #pragma unroll
@@ -1055,10 +1053,8 @@ __global__ __launch_bounds__(256) void eigh_reproject_f64_kernel(EighBlock* bloc
           const float hi = (float)x;
           eb->X[o] = hi;
           eb->W[o] = (float)(x - (double)hi);
-        } else if (STAGE == 1) {
-          eb->A[o] = (float)x;
         } else {
-          eb->X[o] = (float)((row == col ? 1.5 : 0.0) - 0.5 * x);
+          eb->A[o] = (float)x;
         }
       }
 }
@@ -1104,7 +1100,7 @@ __global__ __launch_bounds__(256) void eigh_scaled_off_kernel(EighBlock* blocks,
 
 #include "eigh_cj.hip.h"
 
-// mode 1: eigenvalues = diag(A), eigenvectors = V[:, :n] (cropped to n x n).
+// plain eigenpairs: eigenvalues = diag(A), eigenvectors = V[:, :n] (cropped to n x n).
 __global__ __launch_bounds__(256) void eigh_copy_pairs_kernel(EighBlock* blocks,
                                                               const ETile* tiles) {
   const ETile te = tiles[blockIdx.x];
@@ -1177,9 +1173,6 @@ using psh::Arena;
 
 namespace {
 
-// dev A/B (psh::Options::eigh_small = 0): every size goes through the blocked driver
-bool small_eigh_enabled() { return psh::resolve(nullptr).eigh_small != 0; }
-
 struct EPlan {
   int batch = 0, max_n = 0, max_nb = 0;
   std::vector<int> small_ids;     // blocks solved by eigh_small_kernel
@@ -1239,7 +1232,7 @@ void make_eplan(EPlan& pl, int batch, const int32_t* n, const int32_t* padding_s
     for (int i = 0; i < t; ++i)
       for (int j = 0; j < t; ++j) pl.sq_tiles.push_back({b, (short)i, (short)j, 0, 0});
     for (int c = 0; c < (ne + 63) / 64; ++c) pl.rq_tiles.push_back({b, (short)c, 0, 0, 0});
-    if (ne >= 1 && ne <= SE_MAXN && small_eigh_enabled()) {  // LDS-resident solver, never swept
+    if (ne >= 1 && ne <= SE_MAXN) {  // LDS-resident solver, never swept
       pl.small_ids.push_back(b);
       continue;
     }
@@ -1326,9 +1319,521 @@ extern "C" size_t ps_eigh_root_workspace_bytes(int batch, const int32_t* n) {
   return ecarve(pl, ar, nullptr) + 256;
 }
 
-// mode 0: inverse p-th root (out = val, metrics).  mode 1: plain eigenpairs
-// (out = eigenvectors [n, n] in columns, evals_out = eigenvalues, Jacobi order).
-static int eigh_driver(int mode, void* stream, const float* const* a, const int32_t* n,
+namespace {
+
+enum class EighMode {
+  Root,    // inverse p-th root (out = val, metrics)
+  Pairs,   // plain eigenpairs (out = eigenvectors [n, n] in columns, evals_out = eigenvalues, Jacobi order)
+};
+
+// dynamic LDS of the kernels that need more than the default 64 KB
+constexpr size_t PAIR_LDS = (size_t)(2 * JP * JLD + 2 * JB) * sizeof(float) + 2 * JB * sizeof(int);
+constexpr size_t SMALL_LDS = (size_t)(2 * SE_MAXN * SE_LD + 32 + 256) * sizeof(float);
+constexpr size_t PIVOT_LDS = (size_t)(2 * SE_MAXN * SE_LD + 32 + 3 * SE_MAXN) * sizeof(float);
+constexpr size_t X6_LDS = 6 * (size_t)XPLANE * sizeof(uint16_t);
+
+void set_lds_attributes() {
+  static std::once_flag attr_once;   // kernel attributes are per process (one device per process)
+  std::call_once(attr_once, [] {
+    const auto set = [](const void* fn, size_t lds) {
+      (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    };
+    set((const void*)jacobi_pair_kernel, PAIR_LDS);
+    set((const void*)eigh_small_kernel, SMALL_LDS);
+    set((const void*)cj_pivot_kernel, PIVOT_LDS);
+    set((const void*)cj_update_x6_kernel, X6_LDS);
+  });
+}
+
+// What one call works with: the caller's arguments, the resolved options, the plan, the workspace layout,
+// the host copies of the descriptors, the status ring and what the solvers tell the finish.
+struct EighCall {
+  EighMode mode;
+  hipStream_t st;
+  const float* const* a;
+  const int32_t *n, *lda, *p, *padding_start;
+  int batch;
+  float ridge_epsilon, error_tolerance;
+  int relative_matrix_epsilon;
+  float* const* out; const int32_t* ldo;
+  float* const* evals_out; float* metrics;
+  void* workspace; size_t workspace_bytes;
+  psh::Options opt;
+  float keep_cond = 0.f;       // the keep rule's bound (0: every block's fast-path result stands)
+  EPlan pl; ELayout lo;
+  std::vector<EighBlock> hb;
+  EStatus* status = nullptr;   // this thread's ring of 64 slots
+  int nsq = 0, npair = 0, nrow = 0, ncol = 0;   // tiles of the square, pair, row and column lists
+  bool any_big = false;        // some block has more than 128 rows
+  int gen = 0;                 // status generation of the two-sided solver's waits
+  unsigned pi_expired_before = 0;   // (of the resident power iteration, before this call's)
+  bool td_all = false;         // the tridiagonal path solved every block of more than 128 rows
+  bool td_any = false;         // ... or some of them
+  bool two_sided = false;      // blocks are left for the two-sided solver
+};
+
+const dim3 blk(256);
+dim3 per_block(const EighCall& c) { return dim3((c.batch + 255) / 256); }
+
+// Argument checks, plan (with the keep rule), workspace layout and status ring.
+int validate_and_plan(EighCall& c) {
+  const bool root = c.mode == EighMode::Root;
+  const int batch = c.batch;
+  if (batch <= 0 || !c.a || !c.n || !c.lda || !c.out || !c.ldo || !c.workspace) return PS_EINVAL;
+  if (root && (!c.p || !c.metrics)) return PS_EINVAL;
+  if (!root && !c.evals_out) return PS_EINVAL;
+  for (int b = 0; b < batch; ++b)
+    if (c.n[b] < 1 || c.lda[b] < c.n[b] || c.ldo[b] < c.n[b] || !c.a[b] || !c.out[b] ||
+        (root && c.p[b] < 1) || (!root && !c.evals_out[b]))
+      return PS_EINVAL;
+  if (!root) c.relative_matrix_epsilon = 0;
+  const psh::Options& opt = c.opt;
+  EPlan& pl = c.pl;
+  make_eplan(pl, batch, c.n, c.padding_start);
+  // The keep rule (a block's fast-path result stands only if positive definite with lambda_max / lambda_min
+  // below the bound) applies to plain eigenpairs always and to roots under eigh_solver ACCURATE; AUTO roots
+  // keep every block (the fast path is at or below a true float32 ssyevd's root error: options.h, ps_api.h).
+  const bool keep_rule = !opt.eigh_td_force && (!root || opt.eigh_td_accurate) && opt.eigh_td_max_cond < 3.0e38f;
+  c.keep_cond = keep_rule ? opt.eigh_td_max_cond : 0.f;
+  finish_eplan(pl, false, (root && keep_rule) ? opt.iters_hint : nullptr, opt.iters_hint_stride,
+               2.f * opt.eigh_td_max_cond);
+  pl.pip.set_options(opt);
+  if (pl.max_n > 16384) return PS_EUNSUPPORTED;
+  Arena ar(c.workspace, c.workspace_bytes);
+  ecarve(pl, ar, &c.lo);
+  if (ar.overflow) return PS_EWORKSPACE;
+  c.status = epinned();
+  if (!c.status) return PS_EINTERNAL;
+  set_lds_attributes();
+  c.nsq = (int)pl.sq_tiles.size();
+  c.npair = (int)pl.pair_tiles.size();
+  c.nrow = (int)pl.row_tiles.size();
+  c.ncol = (int)pl.col_tiles.size();
+  c.any_big = c.npair > 0;
+  return PS_OK;
+}
+
+// Host copies of the per-block descriptors; descriptors and tile lists go to the device through the pinned
+// staging ring (no stream synchronisation).
+int fill_and_upload(EighCall& c) {
+  const EPlan& pl = c.pl;
+  const ELayout& lo = c.lo;
+  const bool root = c.mode == EighMode::Root;
+  c.hb.resize(c.batch);
+  for (int b = 0; b < c.batch; ++b) {
+    EighBlock& eb = c.hb[b];
+    memset(&eb, 0, sizeof(eb));
+    eb.a = c.a[b]; eb.out = c.out[b];
+    eb.A = lo.mat[0][b]; eb.V = lo.mat[1][b]; eb.D = lo.mat[2][b]; eb.W = lo.mat[3][b];
+    eb.X = lo.mat[4][b]; eb.Q = lo.Q[b]; eb.offpart = lo.offp[b];
+    eb.sumsq_partial = lo.ssq[b]; eb.evals = lo.evals[b];
+    eb.n = pl.n_eff[b]; eb.n_full = c.n[b]; eb.lda = c.lda[b]; eb.ldo = c.ldo[b];
+    eb.npad = pl.npad[b]; eb.nb = pl.npad[b] / JB; eb.npairs = eb.nb / 2;
+    eb.p = root ? c.p[b] : 1;
+    eb.alpha = (float)(-1.0 / eb.p);
+    eb.evals_out = root ? nullptr : c.evals_out[b];
+    eb.active = eb.n > 0 ? 1 : 0;
+    eb.off_rel = 1.f;
+  }
+  for (int b : pl.small_ids) c.hb[b].small = 1;
+  for (size_t i = 0; i < pl.big_ids.size(); ++i) c.hb[pl.big_ids[i]].cj_group = pl.cj_group_of[i];
+  const struct { void* dev; const void* host; size_t bytes; } tables[] = {
+      {lo.blocks, c.hb.data(), sizeof(EighBlock) * c.hb.size()},
+      {lo.sq, pl.sq_tiles.data(), sizeof(ETile) * pl.sq_tiles.size()},
+      {lo.pair, pl.pair_tiles.data(), sizeof(ETile) * pl.pair_tiles.size()},
+      {lo.row, pl.row_tiles.data(), sizeof(ETile) * pl.row_tiles.size()},
+      {lo.col, pl.col_tiles.data(), sizeof(ETile) * pl.col_tiles.size()},
+      {lo.rq, pl.rq_tiles.data(), sizeof(ETile) * pl.rq_tiles.size()},
+      {lo.small_ids, pl.small_ids.data(), sizeof(int) * pl.small_ids.size()},
+      {lo.chol, pl.chol_tiles.data(), sizeof(ETile) * pl.chol_tiles.size()},
+      {lo.big_ids, pl.big_ids.data(), sizeof(int) * pl.big_ids.size()},
+      {lo.cj_pair[0], pl.cj_pair[0].data(), sizeof(ETile) * pl.cj_pair[0].size()},
+      {lo.cj_row[0], pl.cj_row[0].data(), sizeof(ETile) * pl.cj_row[0].size()},
+      {lo.cj_pair[1], pl.cj_pair[1].data(), sizeof(ETile) * pl.cj_pair[1].size()},
+      {lo.cj_row[1], pl.cj_row[1].data(), sizeof(ETile) * pl.cj_row[1].size()},
+  };
+  for (const auto& t : tables) PS_RC(psh::upload_async(c.st, t.dev, t.host, t.bytes));   // (an empty list is skipped)
+  return PS_OK;
+}
+
+// Power iteration (tol = error_tolerance, DS:996-1001) -> ridge -> D = A + ridge I, A = D, V = I.
+int enqueue_front(EighCall& c) {
+  EPlan& pl = c.pl;
+  const ELayout& lo = c.lo;
+  hipStream_t st = c.st;
+  PS_RC(psh::upload_async(st, lo.blocks, c.hb.data(), sizeof(EighBlock) * c.batch));
+  if (c.relative_matrix_epsilon) {
+    PS_RC(pl.pip.upload(st, c.a, c.lda));
+    // the reference's power iteration is a plain mat-vec loop on the raw input (DS:996-1001)
+    PS_RC(pl.pip.enqueue_symmetry(st, PS_SYMMETRY_VERIFY));
+    PS_RC(pl.pip.enqueue(st, 100, c.error_tolerance));
+  }
+  hipLaunchKernelGGL(eigh_setup_kernel, per_block(c), blk, 0, st, lo.blocks, pl.pip.d_blocks, c.batch,
+                     c.mode == EighMode::Root ? c.ridge_epsilon : 0.f, c.error_tolerance,
+                     c.relative_matrix_epsilon);
+  if (c.nsq > 0) {
+    hipLaunchKernelGGL(eigh_init_kernel, dim3(c.nsq), blk, 0, st, lo.blocks, lo.sq, 0);
+    hipLaunchKernelGGL(eigh_control_kernel, dim3(1), blk, 0, st, lo.blocks, c.batch, 0, 0.f, 0,
+                       (EStatus*)nullptr);
+  }
+  PS_LAUNCH_CHECK();
+  return PS_OK;
+}
+
+// eigh_small_kernel: once converged, G = A V is recomputed with float64 accumulation and the sweeps run on
+constexpr int SMALL_REFRESH = 1;
+
+// n <= 128: whole decomposition in one launch, no host wait
+int enqueue_small(EighCall& c) {
+  if (c.pl.small_ids.empty()) return PS_OK;
+  hipLaunchKernelGGL(eigh_small_kernel, dim3((unsigned)c.pl.small_ids.size()), dim3(SE_T), SMALL_LDS, c.st,
+                     c.lo.blocks, c.lo.small_ids, SMALL_REFRESH);
+  PS_LAUNCH_CHECK();
+  return PS_OK;
+}
+
+// At the first host wait of a call: if the resident power iteration reported an expired wait (PiPlan::health),
+// the ridge of its blocks is NaN and the process is on the streaming power iteration from now on; the front is
+// queued again.  The counter is recorded, so a call starts over at most once.
+int restart_if_pi_expired(EighCall& c, bool* restarted) {
+  *restarted = PiPlan::expired_total() != c.pi_expired_before;
+  if (!*restarted) return PS_OK;
+  PS_RC(enqueue_front(c));
+  PS_RC(enqueue_small(c));
+  c.pi_expired_before = PiPlan::expired_total();
+  return PS_OK;
+}
+
+// Blocks of 129 ... 4096 rows: tridiagonalisation + divide and conquer (eigh_td.hip.h).  One host wait at its
+// end tells whether any block hit an iteration cap.  Blocks it keeps (all of them unless the keep rule applies,
+// see validate_and_plan: then those whose spectrum spans less than eigh_td_max_cond -- a float32
+// tridiagonalisation leaves eps * ||D|| of unstructured error, which the root function amplifies by
+// ||D|| / lambda, exactly as the reference's float32 ssyevd does) are marked td_done and skipped by everything
+// up to the common finish; the others start over on the Jacobi solvers.  Sets td_all and td_any.
+int run_tridiagonal(EighCall& c) {
+  const EPlan& pl = c.pl;
+  ELayout& lo = c.lo;
+  const psh::Options& opt = c.opt;
+  hipStream_t st = c.st;
+  EStatus* slot = &c.status[63];
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    PS_RC(td_run(st, pl.td, lo.td, lo.blocks, c.hb, TD_DEFL_EPS, opt.eigh_td_stage, c.keep_cond,
+                 opt.eigh_td_streams, std::max(0, std::min(opt.eigh_td_tail, TD_TAIL))));
+    slot->gen = -1;
+    hipLaunchKernelGGL(td_status_kernel, dim3(1), dim3(1), 0, st, lo.td.nfail, slot);
+    PS_LAUNCH_CHECK();
+    PS_HIP(hipStreamSynchronize(st));
+    if (slot->gen != 0) return PS_EINTERNAL;
+    bool restarted = false;
+    if (attempt == 0) PS_RC(restart_if_pi_expired(c, &restarted));
+    if (!restarted) break;
+  }
+  const int nbig = (int)pl.big_ids.size();
+  const int redo = slot->active + (nbig - (int)pl.td.ids.size());   // + the blocks above TD_MAXN rows
+  if (opt.eigh_trace)
+    fprintf(stderr, "eigh td: %d of %d block(s) handed to the Jacobi solvers (%d for an iteration cap / "
+                    "non-finite input, the rest for their condition number)\n", redo, nbig, slot->pad_);
+  c.td_all = redo == 0;
+  c.td_any = redo < nbig;
+  if (!c.td_all) {   // those blocks start over: A = D, V = I
+    hipLaunchKernelGGL(eigh_init_kernel, dim3(c.nsq), blk, 0, st, lo.blocks, lo.sq, 1);
+    PS_LAUNCH_CHECK();
+  }
+  return PS_OK;
+}
+
+// The two stream groups of the one-sided sweeps: group 0 on the caller's stream, group 1 on a side stream of
+// the library's pool (common.h), forked behind everything queued on the caller's stream so far.  Whatever way
+// the owner's scope is left (the error returns inside the sweep loop included), the side stream is joined back
+// into the caller's stream: the call stays stream-ordered as a whole.  The events are per host thread (a thread
+// runs one call at a time) and created at first use.
+struct SweepStreams {
+  hipStream_t gs[2] = {nullptr, nullptr};
+  SweepStreams() = default;
+  SweepStreams(const SweepStreams&) = delete;
+  ~SweepStreams() { (void)join(); }
+  // two = false: both groups sweep on the caller's stream
+  int fork(hipStream_t st, bool two) {
+    hipStream_t side = psh::side_stream(0);
+    if (!side) return PS_EINTERNAL;
+    for (hipEvent_t& e : events())
+      if (!e) PS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    gs[0] = st; gs[1] = two ? side : st;
+    if (two) {
+      PS_HIP(hipEventRecord(events()[4], st));
+      PS_HIP(hipStreamWaitEvent(side, events()[4], 0));
+      forked = true;
+    }
+    return PS_OK;
+  }
+  // the end of group g's sweep s (the host waits for it one sweep later)
+  hipEvent_t step(int g, int s) const { return events()[2 * g + (s & 1)]; }
+  int join() {
+    if (!forked) return PS_OK;
+    forked = false;
+    PS_HIP(hipEventRecord(events()[4], gs[1]));
+    PS_HIP(hipStreamWaitEvent(gs[0], events()[4], 0));
+    return PS_OK;
+  }
+
+ private:
+  bool forked = false;
+  static hipEvent_t (&events())[5] {   // [2 g + parity]: steps of group g; [4]: fork / join
+    static thread_local hipEvent_t ev[5] = {};
+    return ev;
+  }
+};
+
+// Arguments of cj_pivot_kernel, and the cap of the outer iteration
+constexpr int CJ_INNER = 2;               // inner sweeps of a pair
+constexpr float CJ_DONE_COS = 1e-3f;      // inner iteration: stop after a sweep below this cosine
+constexpr int CJ_SORT = 1;                // columns leave the pivot sorted by descending norm
+constexpr int CJ_STATIONARY = 1;          // one column of every pair kept in registers
+constexpr float CJ_ONE_BELOW = 0.1f;      // a pair that is already nearly orthogonal gets a single inner sweep
+constexpr int CJ_STORE_TRANSPOSED = 1;    // Q^T: the k-contiguous right operand of cj_update_x6_kernel
+constexpr int CJ_MAX_SWEEPS = 24;         // outer sweeps
+
+// Root mode, blocks of more than 128 rows that the tridiagonal path did not keep: one-sided block Jacobi on
+// the Cholesky factor (eigh_cj.hip.h).  Sets two_sided: some block's factorisation broke down.
+int run_one_sided(EighCall& c) {
+  const EPlan& pl = c.pl;
+  const ELayout& lo = c.lo;
+  const psh::Options& opt = c.opt;
+  hipStream_t st = c.st;
+  EStatus* status = c.status;
+  const int batch = c.batch, nsq = c.nsq;
+  const float cj_tol = opt.eigh_sweep_tol;
+  const int nchol = (int)pl.chol_tiles.size(), nbig = (int)pl.big_ids.size();
+  int gen = 0;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    hipLaunchKernelGGL(cj_select_kernel, per_block(c), blk, 0, st, lo.blocks, batch);
+    hipLaunchKernelGGL(cj_zero_upper_kernel, dim3(nsq), blk, 0, st, lo.blocks, lo.sq);
+    for (int j = 0; j < pl.max_nb; ++j) {
+      hipLaunchKernelGGL(cj_chol_schur_kernel, dim3(nchol), blk, 0, st, lo.blocks, lo.chol, j);
+      hipLaunchKernelGGL(cj_chol_potrf_kernel, dim3(nbig), blk, 0, st, lo.blocks, lo.big_ids, j);
+      hipLaunchKernelGGL(cj_chol_trsm_kernel, dim3(nchol), blk, 0, st, lo.blocks, lo.chol, j);
+    }
+    EStatus* slot = &status[(2 * gen) % 64];
+    slot->gen = -1;
+    hipLaunchKernelGGL(cj_control_kernel, dim3(1), blk, 0, st, lo.blocks, batch, 0, 0.f, gen, slot, -1);
+    PS_LAUNCH_CHECK();
+    PS_HIP(hipStreamSynchronize(st));   // the only stall of the path: fallback blocks known
+    if (slot->gen != gen) return PS_EINTERNAL;
+    ++gen;
+    bool restarted = false;
+    if (attempt == 0) PS_RC(restart_if_pi_expired(c, &restarted));
+    if (restarted) continue;
+    c.two_sided = slot->pad_ > 0;
+    if (opt.eigh_trace)
+      fprintf(stderr, "eigh cj: Cholesky done, %d block(s) fall back to the two-sided solver\n", slot->pad_);
+    break;
+  }
+  // Sweeps.  The blocks are dealt to two groups that sweep on two streams (SweepStreams): the pivot kernel is
+  // LDS / VALU work with one workgroup per CU, the Gram and update kernels are MFMA work with smaller LDS
+  // footprints, so one group's pivots run beside the other group's products on the same CUs
+  // (ps_options.eigh_streams = 1: everything on the caller's stream).  The host stays one sweep ahead of the
+  // GPU (it waits for the status of sweep s - 1 only after sweep s is queued), so the streams never drain;
+  // converged blocks' workgroups exit at once.
+  // Two stream groups by default.  With the x6 update and x6 Gram kernels (61 KB of LDS each: neither fits
+  // beside a 134 KB pivot workgroup) one stream is within +-3 % of two at 64 x 2048^2, faster on one box
+  // (466 vs 476 ms) and slower on the next (500 vs 483); smaller problems gain from two (64 x 1024^2: 72 vs
+  // 80 ms, 256 x 512^2: 50 vs 54 ms).
+  const int nstreams = opt.eigh_streams > 0 ? opt.eigh_streams : 2;
+  SweepStreams ss;
+  PS_RC(ss.fork(st, nstreams >= 2 && !pl.cj_pair[1].empty()));
+  const int first_gen = gen;
+  bool done[2] = {pl.cj_pair[0].empty(), pl.cj_pair[1].empty()};
+  for (int s = 0; s < CJ_MAX_SWEEPS; ++s) {
+    for (int r = 0; r < pl.max_nb - 1; ++r)
+      for (int g = 0; g < 2; ++g) {
+        if (done[g]) continue;
+        const int np_g = (int)pl.cj_pair[g].size(), nr_g = (int)pl.cj_row[g].size();
+        hipLaunchKernelGGL(cj_gram_x3_kernel, dim3(np_g), blk, 0, ss.gs[g], lo.blocks, lo.cj_pair[g], np_g, r);
+        hipLaunchKernelGGL(cj_pivot_kernel, dim3(np_g), dim3(SE_T), PIVOT_LDS, ss.gs[g], lo.blocks,
+                           lo.cj_pair[g], r, cj_tol, CJ_INNER, CJ_DONE_COS * CJ_DONE_COS, CJ_SORT,
+                           CJ_STATIONARY, CJ_ONE_BELOW, CJ_STORE_TRANSPOSED);
+        hipLaunchKernelGGL(cj_update_x6_kernel, dim3(nr_g), blk, X6_LDS, ss.gs[g], lo.blocks, lo.cj_row[g],
+                           nr_g, r);
+      }
+    for (int g = 0; g < 2; ++g) {
+      if (done[g]) continue;
+      EStatus* slot = &status[(2 * gen + g) % 64];
+      slot->gen = -1;
+      hipLaunchKernelGGL(cj_control_kernel, dim3(1), blk, 0, ss.gs[g], lo.blocks, batch, 1, cj_tol, gen,
+                         slot, g);
+      PS_HIP(hipEventRecord(ss.step(g, s), ss.gs[g]));
+    }
+    PS_LAUNCH_CHECK();
+    ++gen;
+    if (s == 0) continue;   // the host reads a sweep's status one sweep later
+    for (int g = 0; g < 2; ++g) {
+      if (done[g]) continue;
+      PS_HIP(hipEventSynchronize(ss.step(g, s - 1)));
+      const EStatus* prev = &status[(2 * (gen - 2) + g) % 64];
+      if (prev->gen != gen - 2) return PS_EINTERNAL;
+      if (opt.eigh_trace)
+        fprintf(stderr, "eigh cj sweep %d group %d: max scaled Gram entry %.3e, %d block(s) still sweeping\n",
+                gen - 2 - first_gen, g, prev->max_off, prev->active);
+      if (prev->active == 0) done[g] = true;
+    }
+    if (done[0] && done[1]) break;
+  }
+  PS_RC(ss.join());
+  hipLaunchKernelGGL(cj_norms_kernel, dim3(nsq), blk, 0, st, lo.blocks, lo.sq);
+  hipLaunchKernelGGL(cj_finalize_kernel, dim3(nsq), blk, 0, st, lo.blocks, lo.sq);
+  PS_LAUNCH_CHECK();
+  return PS_OK;
+}
+
+// One sweep of the blocked two-sided solver: every round of the tournament.
+void sweep(const EighCall& c) {
+  const ELayout& lo = c.lo;
+  for (int r = 0; r < c.pl.max_nb - 1; ++r) {
+    hipLaunchKernelGGL(jacobi_pair_kernel, dim3(c.npair), dim3(JT), PAIR_LDS, c.st, lo.blocks, lo.pair, r, 0);
+    hipLaunchKernelGGL(jacobi_row_kernel, dim3(c.nrow), blk, 0, c.st, lo.blocks, lo.row, c.nrow, r);
+    hipLaunchKernelGGL(jacobi_col_kernel, dim3(c.ncol), blk, 0, c.st, lo.blocks, lo.col, c.ncol, r);
+  }
+}
+
+// The two-sided solver's control kernel in `mode` and the host wait for what it reports (*seen: slot gen % 64).
+int wait_control(EighCall& c, int mode, float tol, const EStatus** seen) {
+  EStatus* slot = &c.status[c.gen % 64];
+  slot->gen = -1;
+  hipLaunchKernelGGL(eigh_control_kernel, dim3(1), blk, 0, c.st, c.lo.blocks, c.batch, mode, tol, c.gen, slot);
+  PS_LAUNCH_CHECK();
+  PS_HIP(hipStreamSynchronize(c.st));
+  if (slot->gen != c.gen) return PS_EINTERNAL;
+  ++c.gen;
+  *seen = slot;
+  return PS_OK;
+}
+
+// Sweeps until no block's pivot off-norm at the START of a sweep is above tol * ||D||: one host wait per sweep
+// (a sweep is tens of ms).
+int run_phase(EighCall& c, float tol, int max_sweeps) {
+  for (int s = 0; s < max_sweeps; ++s) {
+    sweep(c);
+    const EStatus* seen = nullptr;
+    PS_RC(wait_control(c, 1, tol, &seen));
+    if (c.opt.eigh_trace)
+      fprintf(stderr, "eigh sweep %d: tol %.1e max off_rel (start of sweep) %.3e active %d\n", c.gen - 1, tol,
+              seen->max_off, seen->active);
+    if (seen->active == 0) break;
+  }
+  return PS_OK;
+}
+
+// V <- V (1.5 I - 0.5 V^T V): one Newton-Schulz step (two products), then V <-> W.
+void polish(const EighCall& c) {
+  const ELayout& lo = c.lo;
+  hipLaunchKernelGGL((eigh_gemm_kernel<MC, MC>), dim3(c.nsq), blk, 0, c.st, lo.blocks, lo.sq, c.nsq,
+                     (int)GB_V, (int)GB_V, (int)GB_X, (int)GE_POLISH);
+  hipLaunchKernelGGL((eigh_gemm_kernel<KC, MC>), dim3(c.nsq), blk, 0, c.st, lo.blocks, lo.sq, c.nsq,
+                     (int)GB_V, (int)GB_X, (int)GB_W, (int)GE_STORE);
+  hipLaunchKernelGGL(eigh_set_active_kernel, per_block(c), blk, 0, c.st, lo.blocks, c.batch, 1);
+}
+
+// Phase 3 of the two-sided solver: up to EXTRA_SWEEPS more sweeps while a scaled off-diagonal entry is above SCALED_TOL
+constexpr float SCALED_TOL = 1e-5f;
+constexpr int EXTRA_SWEEPS = 4;
+
+// The blocked two-sided solver (eigh.hip's header) for the blocks still active: plain eigenpairs of more than
+// 128 rows that the tridiagonal path did not keep, and roots whose Cholesky factorisation broke down.
+int run_two_sided(EighCall& c) {
+  const ELayout& lo = c.lo;
+  // phase 1: sweep until the pivot off-norm at the start of a sweep < 1e-3 ||D||
+  PS_RC(run_phase(c, 1e-3f, 30));
+  // polish, then A <- V^T D V accumulated in float64 (eigh_reproject_f64_kernel)
+  polish(c);
+  hipLaunchKernelGGL(eigh_reproject_f64_kernel<0>, dim3(4 * c.nsq), blk, 0, c.st, lo.blocks, lo.sq);
+  hipLaunchKernelGGL(eigh_reproject_f64_kernel<1>, dim3(4 * c.nsq), blk, 0, c.st, lo.blocks, lo.sq);
+  PS_LAUNCH_CHECK();
+  // phase 2: finish (quadratic): stop once a sweep STARTED below 1e-4
+  PS_RC(run_phase(c, 1e-4f, 4));
+  // phase 3: the absolute off-norm says nothing about the small eigenvalues of a graded spectrum: sweep on
+  // while the largest SCALED off-diagonal entry is above the float32 floor (well-conditioned inputs are far
+  // below it after phase 2 and skip this)
+  for (int extra = 0; extra <= EXTRA_SWEEPS; ++extra) {
+    hipLaunchKernelGGL(eigh_scaled_off_kernel, dim3(c.nsq), blk, 0, c.st, lo.blocks, lo.sq);
+    const EStatus* seen = nullptr;
+    PS_RC(wait_control(c, 2, SCALED_TOL, &seen));
+    if (c.opt.eigh_trace)
+      fprintf(stderr, "eigh scaled off-diagonal max %.3e, %d block(s) above %.1e\n", seen->max_off,
+              seen->active, SCALED_TOL);
+    if (seen->active == 0 || extra == EXTRA_SWEEPS) break;
+    PS_RC(run_phase(c, 0.f, 1));
+  }
+  return PS_OK;
+}
+
+// From eigenpairs to the outputs: roots and the error metric (DS:1005-1022), or the plain pairs.
+int finish(EighCall& c) {
+  const EPlan& pl = c.pl;
+  const ELayout& lo = c.lo;
+  const psh::Options& opt = c.opt;
+  hipStream_t st = c.st;
+  const int nsq = c.nsq, batch = c.batch;
+  const bool root = c.mode == EighMode::Root;
+  if (nsq > 0) {
+    // the sweeps after the re-projection let V drift from orthogonality again by a few eps32 per sweep: one
+    // more Newton-Schulz step takes most graded / rank-deficient cases to LAPACK-float32's error to three
+    // digits.  Not after the one-sided sweeps alone: U is orthogonal to the sweep tolerance there (root error
+    // unchanged to three digits on every test spectrum).
+    if (c.two_sided) polish(c);
+    if (c.td_any) {   // the finish of the one-sided path (Rayleigh quotients from D V) applies to them
+      hipLaunchKernelGGL(td_mark_cj_kernel, per_block(c), blk, 0, st, lo.blocks, batch);
+      PS_LAUNCH_CHECK();
+    }
+    // One-sided or tridiagonal path only (no small blocks, no fallback): D U is formed ONCE, float64-accumulated
+    // on the float64 MFMA as a float32 hi/lo pair; the Rayleigh quotients, and the error metric's product
+    // U^T (D U), are taken from it (39 + 8.6 ms of float64 VALU dot products and a float32 D U product
+    // become 20 ms).
+    // The float64 Rayleigh quotients stay after the one-sided sweeps (eigh_cj_refine): |g_j|^2 drifts by ~1e-5
+    // relative over the ~300 float32 updates of a column, which is 0.1-0.2 absolute on eigenvalues of 1e4 in
+    // the error metric max|u^T D u - diag(e)| (DS:1017-1021, failure threshold 0.1), and the refined values
+    // are 20-30 % closer to float64 on rank-deficient-plus-ridge inputs.
+    const bool fused = (opt.eigh_cj || c.td_all) && root && c.any_big && !c.two_sided &&
+                       pl.small_ids.empty() && opt.eigh_cj_refine;
+    if (fused) {
+      hipLaunchKernelGGL(eigh_reproject_f64_kernel<0>, dim3(4 * nsq), blk, 0, st, lo.blocks, lo.sq);
+      hipLaunchKernelGGL(cj_rayleigh_from_dv_kernel, dim3(nsq), blk, 0, st, lo.blocks, lo.sq);
+      hipLaunchKernelGGL(eigh_scale_kernel, dim3(nsq), blk, 0, st, lo.blocks, lo.sq);
+      hipLaunchKernelGGL((eigh_gemm_kernel<KC, KC>), dim3(nsq), blk, 0, st, lo.blocks, lo.sq, nsq,
+                         (int)GB_W, (int)GB_W, (int)GB_OUT, (int)GE_SYM_STORE);
+      hipLaunchKernelGGL((eigh_gemm_kernel<MC, MC>), dim3(nsq), blk, 0, st, lo.blocks, lo.sq, nsq,
+                         (int)GB_V, (int)GB_X, (int)GB_A, (int)GE_ERR_UPPER);
+    } else {
+      if (opt.eigh_refine && !pl.rq_tiles.empty() &&
+          (c.two_sided || opt.eigh_cj_refine || !pl.small_ids.empty())) {
+        hipLaunchKernelGGL(eigh_rayleigh_f64_kernel, dim3((unsigned)pl.rq_tiles.size()), blk, 0, st,
+                           lo.blocks, lo.rq);
+        PS_LAUNCH_CHECK();
+      }
+      if (!root) {
+        hipLaunchKernelGGL(eigh_copy_pairs_kernel, dim3(nsq), blk, 0, st, lo.blocks, lo.sq);
+        PS_LAUNCH_CHECK();
+        return PS_OK;
+      }
+      // root and error metric
+      hipLaunchKernelGGL(eigh_scale_kernel, dim3(nsq), blk, 0, st, lo.blocks, lo.sq);
+      hipLaunchKernelGGL((eigh_gemm_kernel<KC, KC>), dim3(nsq), blk, 0, st, lo.blocks, lo.sq, nsq,
+                         (int)GB_W, (int)GB_W, (int)GB_OUT, (int)GE_STORE);
+      hipLaunchKernelGGL((eigh_gemm_kernel<KC, MC>), dim3(nsq), blk, 0, st, lo.blocks, lo.sq, nsq,
+                         (int)GB_D, (int)GB_V, (int)GB_X, (int)GE_STORE);
+      hipLaunchKernelGGL((eigh_gemm_kernel<MC, MC>), dim3(nsq), blk, 0, st, lo.blocks, lo.sq, nsq,
+                         (int)GB_V, (int)GB_X, (int)GB_A, (int)GE_ERR);
+    }
+  }
+  if (!root) return PS_OK;
+  hipLaunchKernelGGL(eigh_zero_out_kernel, dim3(batch, 16), blk, 0, st, lo.blocks);
+  hipLaunchKernelGGL(eigh_metrics_kernel, dim3(batch), dim3(64), 0, st, lo.blocks, batch, c.metrics);
+  PS_LAUNCH_CHECK();
+  return PS_OK;
+}
+
+}  // namespace
+
+static int eigh_driver(EighMode mode, void* stream, const float* const* a, const int32_t* n,
                        const int32_t* lda, const int32_t* p, const int32_t* padding_start,
                        int batch, float ridge_epsilon, float error_tolerance,
                        int relative_matrix_epsilon, float* const* out, const int32_t* ldo,
@@ -1338,507 +1843,23 @@ static int eigh_driver(int mode, void* stream, const float* const* a, const int3
   bool bad_options = false;
   const psh::Options opt = psh::resolve(options, &bad_options);
   if (bad_options) return PS_EINVAL;
-  if (batch <= 0 || !a || !n || !lda || !out || !ldo || !workspace) return PS_EINVAL;
-  if (mode == 0 && (!p || !metrics)) return PS_EINVAL;
-  if (mode == 1 && !evals_out) return PS_EINVAL;
-  for (int b = 0; b < batch; ++b)
-    if (n[b] < 1 || lda[b] < n[b] || ldo[b] < n[b] || !a[b] || !out[b] ||
-        (mode == 0 && p[b] < 1) || (mode == 1 && !evals_out[b]))
-      return PS_EINVAL;
-  if (mode == 1) relative_matrix_epsilon = 0;
-  hipStream_t st = (hipStream_t)stream;
-  EPlan pl;
-  make_eplan(pl, batch, n, padding_start);
-  // The keep rule (a block's fast-path result stands only if positive definite with lambda_max / lambda_min
-  // below the bound) applies to plain eigenpairs always and to roots under eigh_solver ACCURATE; AUTO roots
-  // keep every block (the fast path is at or below a true float32 ssyevd's root error: options.h, ps_api.h).
-  const bool keep_rule = !opt.eigh_td_force && (mode == 1 || opt.eigh_td_accurate) &&
-                         opt.eigh_td_max_cond < 3.0e38f;
-  const float keep_cond = keep_rule ? opt.eigh_td_max_cond : 0.f;
-  finish_eplan(pl, false, (mode == 0 && keep_rule) ? opt.iters_hint : nullptr, opt.iters_hint_stride,
-               2.f * opt.eigh_td_max_cond);
-  pl.pip.set_options(opt);
-  if (pl.max_n > 16384) return PS_EUNSUPPORTED;
-  Arena ar(workspace, workspace_bytes);
-  ELayout lo;
-  ecarve(pl, ar, &lo);
-  if (ar.overflow) return PS_EWORKSPACE;
-  EStatus* status = epinned();
-  if (!status) return PS_EINTERNAL;
-  const size_t pair_lds = (size_t)(2 * JP * JLD + 2 * JB) * sizeof(float) + 2 * JB * sizeof(int);
-  static bool attr_set = false;
-  if (!attr_set) {
-    PS_HIP(hipFuncSetAttribute((const void*)jacobi_pair_kernel,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)pair_lds));
-    attr_set = true;
+  EighCall c{mode, (hipStream_t)stream, a, n, lda, p, padding_start, batch, ridge_epsilon, error_tolerance,
+             relative_matrix_epsilon, out, ldo, evals_out, metrics, workspace, workspace_bytes, opt};
+  PS_RC(validate_and_plan(c));
+  PS_RC(fill_and_upload(c));
+  c.pi_expired_before = PiPlan::expired_total();
+  PS_RC(enqueue_front(c));
+  if (c.nsq > 0) PS_RC(enqueue_small(c));
+  // plain eigenpairs of small blocks only: eigh_small_kernel wrote sorted pairs to the outputs
+  if (mode == EighMode::Pairs && !c.any_big) return PS_OK;
+  if (c.any_big) {   // blocks of more than 128 rows
+    if (opt.eigh_td && !c.pl.td.empty()) PS_RC(run_tridiagonal(c));
+    c.two_sided = !c.td_all;
+    // (PS_EIGH_CJ=0 / eigh_solver TWO_SIDED: the blocked two-sided solver for everything)
+    if (opt.eigh_cj && mode == EighMode::Root && !c.td_all) PS_RC(run_one_sided(c));
+    if (c.two_sided) PS_RC(run_two_sided(c));
   }
-
-  std::vector<EighBlock> hb(batch);
-  for (int b = 0; b < batch; ++b) {
-    EighBlock& eb = hb[b];
-    memset(&eb, 0, sizeof(eb));
-    eb.a = a[b]; eb.out = out[b];
-    eb.A = lo.mat[0][b]; eb.V = lo.mat[1][b]; eb.D = lo.mat[2][b]; eb.W = lo.mat[3][b];
-    eb.X = lo.mat[4][b]; eb.Q = lo.Q[b]; eb.offpart = lo.offp[b];
-    eb.sumsq_partial = lo.ssq[b]; eb.evals = lo.evals[b];
-    eb.n = pl.n_eff[b]; eb.n_full = n[b]; eb.lda = lda[b]; eb.ldo = ldo[b];
-    eb.npad = pl.npad[b]; eb.nb = pl.npad[b] / JB; eb.npairs = eb.nb / 2;
-    eb.p = mode == 0 ? p[b] : 1;
-    eb.alpha = (float)(-1.0 / eb.p);
-    eb.evals_out = mode == 1 ? evals_out[b] : nullptr;
-    eb.active = eb.n > 0 ? 1 : 0;
-    eb.off_rel = 1.f;
-  }
-  for (int b : pl.small_ids) hb[b].small = 1;
-  for (size_t i = 0; i < pl.big_ids.size(); ++i) hb[pl.big_ids[i]].cj_group = pl.cj_group_of[i];
-  auto up = [&](void* d, const void* h, size_t bytes) -> int {
-    return psh::upload_async(st, d, h, bytes);  // pinned staging ring: no stream synchronisation
-  };
-  int rc;
-  if ((rc = up(lo.blocks, hb.data(), sizeof(EighBlock) * batch))) return rc;
-  if ((rc = up(lo.sq, pl.sq_tiles.data(), sizeof(ETile) * pl.sq_tiles.size()))) return rc;
-  if ((rc = up(lo.pair, pl.pair_tiles.data(), sizeof(ETile) * pl.pair_tiles.size()))) return rc;
-  if ((rc = up(lo.row, pl.row_tiles.data(), sizeof(ETile) * pl.row_tiles.size()))) return rc;
-  if ((rc = up(lo.col, pl.col_tiles.data(), sizeof(ETile) * pl.col_tiles.size()))) return rc;
-  if (!pl.rq_tiles.empty() &&
-      (rc = up(lo.rq, pl.rq_tiles.data(), sizeof(ETile) * pl.rq_tiles.size())))
-    return rc;
-  if (!pl.small_ids.empty() &&
-      (rc = up(lo.small_ids, pl.small_ids.data(), sizeof(int) * pl.small_ids.size())))
-    return rc;
-  if (!pl.chol_tiles.empty() &&
-      (rc = up(lo.chol, pl.chol_tiles.data(), sizeof(ETile) * pl.chol_tiles.size())))
-    return rc;
-  if (!pl.big_ids.empty() &&
-      (rc = up(lo.big_ids, pl.big_ids.data(), sizeof(int) * pl.big_ids.size())))
-    return rc;
-  for (int g = 0; g < 2; ++g) {
-    if (!pl.cj_pair[g].empty() &&
-        (rc = up(lo.cj_pair[g], pl.cj_pair[g].data(), sizeof(ETile) * pl.cj_pair[g].size())))
-      return rc;
-    if (!pl.cj_row[g].empty() &&
-        (rc = up(lo.cj_row[g], pl.cj_row[g].data(), sizeof(ETile) * pl.cj_row[g].size())))
-      return rc;
-  }
-  const int nsq = (int)pl.sq_tiles.size();
-  const int npair = (int)pl.pair_tiles.size();
-  const int nrow = (int)pl.row_tiles.size(), ncol = (int)pl.col_tiles.size();
-  const dim3 blk(256);
-
-  // Power iteration (tol = error_tolerance, DS:996-1001) -> ridge -> D = A + ridge I.  Queued
-  // again (on the streaming power iteration) if the resident one reports an expired wait at the
-  // first host wait of the call (PiPlan::health).
-  unsigned pi_expired_before = PiPlan::expired_total();
-  auto enqueue_front = [&]() -> int {
-    int rc2;
-    if ((rc2 = up(lo.blocks, hb.data(), sizeof(EighBlock) * batch))) return rc2;
-    if (relative_matrix_epsilon) {
-      if ((rc2 = pl.pip.upload(st, a, lda))) return rc2;
-      // the reference's power iteration is a plain mat-vec loop on the raw input (DS:996-1001)
-      if ((rc2 = pl.pip.enqueue_symmetry(st, PS_SYMMETRY_VERIFY))) return rc2;
-      if ((rc2 = pl.pip.enqueue(st, 100, error_tolerance))) return rc2;
-    }
-    hipLaunchKernelGGL(eigh_setup_kernel, dim3((batch + 255) / 256), blk, 0, st, lo.blocks,
-                       pl.pip.d_blocks, batch, mode == 0 ? ridge_epsilon : 0.f, error_tolerance,
-                       relative_matrix_epsilon);
-    if (nsq > 0) {
-      hipLaunchKernelGGL(eigh_init_kernel, dim3(nsq), blk, 0, st, lo.blocks, lo.sq, 0);
-      hipLaunchKernelGGL(eigh_control_kernel, dim3(1), blk, 0, st, lo.blocks, batch, 0, 0.f, 0,
-                         (EStatus*)nullptr);
-    }
-    PS_LAUNCH_CHECK();
-    return 0;
-  };
-  if ((rc = enqueue_front())) return rc;
-
-  if (nsq > 0) {
-    auto sweep = [&]() {
-      for (int r = 0; r < pl.max_nb - 1; ++r) {
-        hipLaunchKernelGGL(jacobi_pair_kernel, dim3(npair), dim3(JT), pair_lds, st, lo.blocks,
-                           lo.pair, r, 0);
-        hipLaunchKernelGGL(jacobi_row_kernel, dim3(nrow), blk, 0, st, lo.blocks, lo.row, nrow, r);
-        hipLaunchKernelGGL(jacobi_col_kernel, dim3(ncol), blk, 0, st, lo.blocks, lo.col, ncol, r);
-      }
-    };
-    int gen = 0;
-    auto run_phase = [&](float tol, int max_sweeps) -> int {
-      for (int s = 0; s < max_sweeps; ++s) {
-        EStatus* slot = &status[gen % 64];
-        slot->gen = -1;
-        sweep();
-        hipLaunchKernelGGL(eigh_control_kernel, dim3(1), blk, 0, st, lo.blocks, batch, 1, tol,
-                           gen, slot);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-        e = hipStreamSynchronize(st);  // one sync per sweep (a sweep is tens of ms)
-        if (e != hipSuccess) return (int)e;
-        if (slot->gen != gen) return PS_EINTERNAL;
-        if (opt.eigh_trace)
-          fprintf(stderr, "eigh sweep %d: tol %.1e max off_rel (start of sweep) %.3e active %d\n",
-                  gen, tol, slot->max_off, slot->active);
-        ++gen;
-        if (slot->active == 0) break;
-      }
-      return 0;
-    };
-    const bool any_big = npair > 0;
-    auto enqueue_small = [&]() -> int {
-    if (!pl.small_ids.empty()) {  // n <= 128: whole decomposition in one launch, no host wait
-        const size_t small_lds = (size_t)(2 * SE_MAXN * SE_LD + 32 + 256) * sizeof(float);
-        static bool small_attr = false;
-        if (!small_attr) {
-          PS_HIP(hipFuncSetAttribute((const void*)eigh_small_kernel,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_lds));
-          small_attr = true;
-        }
-        const int small_refresh = opt.eigh_small_refresh;
-        hipLaunchKernelGGL(eigh_small_kernel, dim3((unsigned)pl.small_ids.size()), dim3(SE_T),
-                           small_lds, st, lo.blocks, lo.small_ids, small_refresh);
-        PS_LAUNCH_CHECK();
-      }
-      return 0;
-    };
-    if ((rc = enqueue_small())) return rc;
-    if (mode == 1 && !any_big) return PS_OK;  // the kernel wrote sorted pairs to the outputs
-    // Root mode, blocks of more than 128 rows: one-sided block Jacobi on the Cholesky factor
-    // (eigh_cj.hip.h).  PS_EIGH_CJ=0 restores the blocked two-sided solver for everything.
-    const int cj_on = opt.eigh_cj;
-    bool run_two_sided = any_big;
-    // After the one-sided sweeps U is orthogonal to the sweep tolerance, so the Newton-Schulz polish
-    // of the two-sided solver is off (root error unchanged to three digits on every test
-    // spectrum).  The float64 Rayleigh quotients stay: |g_j|^2 drifts by ~1e-5 relative over the
-    // ~300 float32 updates of a column, which is 0.1-0.2 absolute on eigenvalues of 1e4 in the
-    // error metric max|u^T D u - diag(e)| (DS:1017-1021, failure threshold 0.1), and the refined
-    // values are 20-30 % closer to float64 on rank-deficient-plus-ridge inputs.
-    const int cj_refine = opt.eigh_cj_refine;
-    const int cj_polish = opt.eigh_cj_polish;
-    // Blocks of 129 ... 4096 rows: tridiagonalisation + divide and conquer (eigh_td.hip.h).  One host
-    // wait at its end tells whether any block hit an iteration cap (or the resident power iteration
-    // expired); such a call starts over on the Jacobi solvers below.
-    // Blocks it keeps (all of them unless the keep rule applies, see keep_cond above: then those whose
-    // spectrum spans less than eigh_td_max_cond -- a float32 tridiagonalisation leaves eps * ||D|| of
-    // unstructured error, which the root function amplifies by ||D|| / lambda, exactly as the reference's
-    // float32 ssyevd does) are marked td_done and skipped by everything between here and the common
-    // finish; the others start over on the Jacobi solvers.
-    bool td_all = false;   // every block of more than 128 rows is done
-    bool td_any = false;
-    if (opt.eigh_td && any_big && !pl.td.empty()) {
-      for (int attempt = 0; attempt < 2; ++attempt) {
-        if ((rc = td_run(st, pl.td, lo.td, lo.blocks, hb, opt.eigh_td_defl_eps, opt.eigh_td_stage,
-                         keep_cond, opt.eigh_td_streams,
-                         std::max(0, std::min(opt.eigh_td_tail, TD_TAIL)))))
-          return rc;
-        EStatus* slot = &status[63];
-        slot->gen = -1;
-        hipLaunchKernelGGL(td_status_kernel, dim3(1), dim3(1), 0, st, lo.td.nfail, slot);
-        PS_LAUNCH_CHECK();
-        PS_HIP(hipStreamSynchronize(st));
-        if (slot->gen != 0) return PS_EINTERNAL;
-        if (attempt == 0 && PiPlan::expired_total() != pi_expired_before) {
-          if ((rc = enqueue_front())) return rc;   // ridge of some blocks is NaN: streaming power iteration now
-          if ((rc = enqueue_small())) return rc;
-          pi_expired_before = PiPlan::expired_total();   // handled here: the Jacobi path below must not start over
-          continue;
-        }
-        const int nbig = (int)pl.big_ids.size();
-        const int redo = slot->active + (nbig - (int)pl.td.ids.size());   // + the blocks above TD_MAXN rows
-        if (opt.eigh_trace)
-          fprintf(stderr, "eigh td: %d of %d block(s) handed to the Jacobi solvers (%d for an iteration cap / "
-                          "non-finite input, the rest for their condition number)\n", redo, nbig, slot->pad_);
-        td_all = redo == 0;
-        td_any = redo < nbig;
-        if (!td_all) {   // those blocks start over: A = D, V = I
-          hipLaunchKernelGGL(eigh_init_kernel, dim3(nsq), blk, 0, st, lo.blocks, lo.sq, 1);
-          PS_LAUNCH_CHECK();
-        }
-        break;
-      }
-    }
-    const bool td_done = td_all;
-    if (td_done) run_two_sided = false;
-    if (cj_on && mode == 0 && any_big && !td_done) {
-      const float cj_tol = opt.eigh_sweep_tol;
-      const int cj_inner = opt.eigh_cj_inner;
-      const float cj_done = opt.eigh_cj_done;   // inner iteration: stop after a sweep below this cosine
-      const int cj_max_sweeps = opt.eigh_cj_max_sweeps;
-      const int cj_stationary = opt.eigh_cj_stationary;
-      const float cj_one_below = opt.eigh_cj_one_below;
-      const int cj_sort = opt.eigh_cj_sort;
-      const size_t piv_lds = (size_t)(2 * SE_MAXN * SE_LD + 32 + 3 * SE_MAXN) * sizeof(float);
-      static bool piv_attr = false;
-      if (!piv_attr) {
-        PS_HIP(hipFuncSetAttribute((const void*)cj_pivot_kernel,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)piv_lds));
-        piv_attr = true;
-      }
-      static thread_local hipEvent_t cj_ev[2] = {nullptr, nullptr};
-      for (int i = 0; i < 2; ++i)
-        if (!cj_ev[i]) PS_HIP(hipEventCreateWithFlags(&cj_ev[i], hipEventDisableTiming));
-      const int nchol = (int)pl.chol_tiles.size(), nbig = (int)pl.big_ids.size();
-      int gen = 0;
-      for (int attempt = 0; attempt < 2; ++attempt) {
-        hipLaunchKernelGGL(cj_select_kernel, dim3((batch + 255) / 256), blk, 0, st, lo.blocks, batch);
-        hipLaunchKernelGGL(cj_zero_upper_kernel, dim3(nsq), blk, 0, st, lo.blocks, lo.sq);
-        for (int j = 0; j < pl.max_nb; ++j) {
-          hipLaunchKernelGGL(cj_chol_schur_kernel, dim3(nchol), blk, 0, st, lo.blocks, lo.chol, j);
-          hipLaunchKernelGGL(cj_chol_potrf_kernel, dim3(nbig), blk, 0, st, lo.blocks, lo.big_ids, j);
-          hipLaunchKernelGGL(cj_chol_trsm_kernel, dim3(nchol), blk, 0, st, lo.blocks, lo.chol, j);
-        }
-        EStatus* slot = &status[(2 * gen) % 64];
-        slot->gen = -1;
-        hipLaunchKernelGGL(cj_control_kernel, dim3(1), blk, 0, st, lo.blocks, batch, 0, 0.f, gen,
-                           slot, -1);
-        PS_LAUNCH_CHECK();
-        PS_HIP(hipStreamSynchronize(st));   // the only stall of the path: fallback blocks known
-        if (slot->gen != gen) return PS_EINTERNAL;
-        ++gen;
-        if (attempt == 0 && PiPlan::expired_total() != pi_expired_before) {
-          // the resident power iteration gave up (see PiPlan::health): the ridge of its blocks
-          // is NaN.  The process is on the streaming execution now: queue the front again.
-          if ((rc = enqueue_front())) return rc;
-          if ((rc = enqueue_small())) return rc;
-          continue;
-        }
-        run_two_sided = slot->pad_ > 0;
-        if (opt.eigh_trace)
-          fprintf(stderr, "eigh cj: Cholesky done, %d block(s) fall back to the two-sided solver\n",
-                  slot->pad_);
-        break;
-      }
-      // Sweeps.  The blocks are dealt to two groups that sweep on two streams (the caller's and
-      // a side stream of this thread): the pivot kernel is LDS / VALU work with one workgroup
-      // per CU, the Gram and update kernels are MFMA work with small LDS footprints, so one
-      // group's pivots run beside the other group's products on the same CUs (PS_EIGH_CJ_STREAMS=1:
-      // everything on the caller's stream).  The host stays one sweep ahead of the GPU (it waits
-      // for the status of sweep s - 1 only after sweep s is queued), so the streams never
-      // drain; converged blocks' workgroups exit at once.
-      // Two stream groups by default.  With the x6 update and x6 Gram kernels (61 KB of LDS each: neither
-      // fits beside a 134 KB pivot workgroup) one stream is within +-3 % of two at 64 x 2048^2, faster on
-      // one box (466 vs 476 ms) and slower on the next (500 vs 483); smaller problems gain from two
-      // (64 x 1024^2: 72 vs 80 ms, 256 x 512^2: 50 vs 54 ms).
-      const int nstreams = opt.eigh_streams > 0 ? opt.eigh_streams : 2;
-      hipStream_t side = psh::side_stream(0);   // the library's shared pool (common.h)
-      static thread_local hipEvent_t side_ev[3] = {nullptr, nullptr, nullptr};
-      if (!side) return PS_EINTERNAL;
-      for (int i = 0; i < 3; ++i)
-        if (!side_ev[i]) PS_HIP(hipEventCreateWithFlags(&side_ev[i], hipEventDisableTiming));
-      // K-tile depth of the update products: 8 = 20 KB of LDS, which fits beside a pivot workgroup
-      const int cj_ubk = opt.eigh_cj_ubk;
-      // arithmetic of the update products [G_I G_J] Q: 1 = three-way bf16 split on the bf16 MFMA
-      const int cj_x6 = opt.eigh_update_bf16x6;
-      constexpr size_t x6_lds = 6 * (size_t)XPLANE * sizeof(uint16_t);
-      if (cj_x6) {
-        static std::once_flag x6_once;
-        std::call_once(x6_once, [] {
-          (void)hipFuncSetAttribute((const void*)cj_update_x6_kernel,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)x6_lds);
-        });
-      }
-      const bool two = nstreams >= 2 && !pl.cj_pair[1].empty();
-      hipStream_t gs[2] = {st, two ? side : st};
-      // Whatever way this scope is left (the error returns inside the sweep loop included), the side
-      // stream is joined back into the caller's stream: the call stays stream-ordered as a whole.
-      struct SideJoin {
-        hipStream_t st, side; hipEvent_t ev; bool forked;
-        ~SideJoin() {
-          if (forked && hipEventRecord(ev, side) == hipSuccess) (void)hipStreamWaitEvent(st, ev, 0);
-        }
-      } side_join{st, side, side_ev[2], false};
-      if (two) {   // everything queued so far on the caller's stream happens before the side stream starts
-        PS_HIP(hipEventRecord(side_ev[2], st));
-        PS_HIP(hipStreamWaitEvent(side, side_ev[2], 0));
-        side_join.forked = true;
-      }
-      const int first_gen = gen;
-      bool done[2] = {pl.cj_pair[0].empty(), pl.cj_pair[1].empty()};
-      // Gram arithmetic per group and sweep: bf16x3 while the last KNOWN largest scaled entry of
-      // the group (one sweep behind the GPU) is above cj_x3_above; float32 afterwards, and always
-      // for the sweep that may stop (cj_gram_x3_kernel's comment).  OFF by default (threshold 0): a
-      // conservative 5e-2 (the first 3-4 of ~10 sweeps) buys 1 % and still costs accuracy on small
-      // blocks whose few sweeps outrun the one-sweep lag of `known_off` (200^2 Wishart: 3.7e-6 vs
-      // 1.5e-6 from float64); with 3e-3 / 1e-3 the step is 4-7 % faster
-      // (472 / 460 vs 495 ms for 64 x 2048^2) but the root ends 2 x further from float64 (7.6e-6
-      // vs 4.2e-6; 1000^2: 5.9e-6 vs 2.7e-6) -- the float32 sweeps that follow a noisy phase start
-      // from 1e-5-level entries, and with the clustered eigenvalues of these spectra ONE sweep
-      // takes them just under the 2e-6 stop tolerance instead of far below it as the gradual
-      // float32 descent does.
-      const float cj_x3_above = opt.eigh_gram_x3_above;
-      float known_off[2] = {1.f, 1.f};
-      for (int s = 0; s < cj_max_sweeps; ++s) {
-        for (int r = 0; r < pl.max_nb - 1; ++r)
-          for (int g = 0; g < 2; ++g) {
-            if (done[g]) continue;
-            const int np_g = (int)pl.cj_pair[g].size(), nr_g = (int)pl.cj_row[g].size();
-            const bool x3 = cj_x3_above > 0.f && known_off[g] > cj_x3_above;
-            if (x3)
-              hipLaunchKernelGGL(cj_gram_x3_kernel<2>, dim3(np_g), blk, 0, gs[g], lo.blocks,
-                                 lo.cj_pair[g], np_g, r);
-            else if (opt.eigh_gram_bf16x6)
-              hipLaunchKernelGGL(cj_gram_x3_kernel<3>, dim3(np_g), blk, 0, gs[g], lo.blocks,
-                                 lo.cj_pair[g], np_g, r);
-            else
-              hipLaunchKernelGGL(cj_gram_kernel, dim3(np_g), blk, 0, gs[g], lo.blocks, lo.cj_pair[g],
-                                 np_g, r);
-            // on a bf16 Gram matrix entries below its noise floor (~1e-5 scaled) are not rotated:
-            // a rotation by noise would undo what the pair has already converged to
-            hipLaunchKernelGGL(cj_pivot_kernel, dim3(np_g), dim3(SE_T), piv_lds, gs[g], lo.blocks,
-                               lo.cj_pair[g], r, x3 ? fmaxf(cj_tol, opt.eigh_gram_x3_skip) : cj_tol, cj_inner, cj_done * cj_done, cj_sort,
-                               cj_stationary, cj_one_below, cj_x6);
-            if (cj_x6)
-              hipLaunchKernelGGL(cj_update_x6_kernel, dim3(nr_g), blk, x6_lds, gs[g], lo.blocks,
-                                 lo.cj_row[g], nr_g, r);
-            else if (cj_ubk == 8)
-              hipLaunchKernelGGL(cj_update_kernel_t<8>, dim3(nr_g), blk, 0, gs[g], lo.blocks,
-                                 lo.cj_row[g], nr_g, r);
-            else
-              hipLaunchKernelGGL(cj_update_kernel_t<16>, dim3(nr_g), blk, 0, gs[g], lo.blocks,
-                                 lo.cj_row[g], nr_g, r);
-          }
-        for (int g = 0; g < 2; ++g) {
-          if (done[g]) continue;
-          EStatus* slot = &status[(2 * gen + g) % 64];
-          slot->gen = -1;
-          hipLaunchKernelGGL(cj_control_kernel, dim3(1), blk, 0, gs[g], lo.blocks, batch, 1, cj_tol,
-                             gen, slot, g);
-          PS_HIP(hipEventRecord(g == 0 ? cj_ev[s & 1] : side_ev[s & 1], gs[g]));
-        }
-        PS_LAUNCH_CHECK();
-        ++gen;
-        if (s >= 1) {
-          for (int g = 0; g < 2; ++g) {
-            if (done[g]) continue;
-            PS_HIP(hipEventSynchronize(g == 0 ? cj_ev[(s - 1) & 1] : side_ev[(s - 1) & 1]));
-            EStatus* prev = &status[(2 * (gen - 2) + g) % 64];
-            if (prev->gen != gen - 2) return PS_EINTERNAL;
-            if (opt.eigh_trace)
-              fprintf(stderr, "eigh cj sweep %d group %d: max scaled Gram entry %.3e, %d block(s) still sweeping\n",
-                      gen - 2 - first_gen, g, prev->max_off, prev->active);
-            known_off[g] = prev->max_off;
-            if (prev->active == 0) done[g] = true;
-          }
-          if (done[0] && done[1]) break;
-        }
-      }
-      if (two) {
-        side_join.forked = false;
-        PS_HIP(hipEventRecord(side_ev[2], side));
-        PS_HIP(hipStreamWaitEvent(st, side_ev[2], 0));
-      }
-      hipLaunchKernelGGL(cj_norms_kernel, dim3(nsq), blk, 0, st, lo.blocks, lo.sq);
-      hipLaunchKernelGGL(cj_finalize_kernel, dim3(nsq), blk, 0, st, lo.blocks, lo.sq);
-      PS_LAUNCH_CHECK();
-    }
-    if (run_two_sided) {
-    // phase 1: sweep until the pivot off-norm at the start of a sweep < 1e-3 ||D||
-    if (any_big && (rc = run_phase(1e-3f, 30))) return rc;
-    // polish: V <- V (1.5 I - 0.5 V^T V);  A <- V^T D V
-    hipLaunchKernelGGL((eigh_gemm_kernel<MC, MC>), dim3(nsq), blk, 0, st, lo.blocks, lo.sq, nsq,
-                       (int)GB_V, (int)GB_V, (int)GB_X, (int)GE_POLISH);
-    hipLaunchKernelGGL((eigh_gemm_kernel<KC, MC>), dim3(nsq), blk, 0, st, lo.blocks, lo.sq, nsq,
-                       (int)GB_V, (int)GB_X, (int)GB_W, (int)GE_STORE);
-    hipLaunchKernelGGL(eigh_set_active_kernel, dim3((batch + 255) / 256), blk, 0, st, lo.blocks,
-                       batch, 1);  // V <-> W
-    const int f64_reproject = opt.eigh_f64_reproject;
-    if (f64_reproject && any_big) {
-      hipLaunchKernelGGL(eigh_reproject_f64_kernel<0>, dim3(4 * nsq), blk, 0, st, lo.blocks, lo.sq);
-      hipLaunchKernelGGL(eigh_reproject_f64_kernel<1>, dim3(4 * nsq), blk, 0, st, lo.blocks, lo.sq);
-    } else {
-      hipLaunchKernelGGL((eigh_gemm_kernel<KC, MC>), dim3(nsq), blk, 0, st, lo.blocks, lo.sq, nsq,
-                         (int)GB_D, (int)GB_V, (int)GB_X, (int)GE_STORE);
-      hipLaunchKernelGGL((eigh_gemm_kernel<MC, MC>), dim3(nsq), blk, 0, st, lo.blocks, lo.sq, nsq,
-                         (int)GB_V, (int)GB_X, (int)GB_A, (int)GE_STORE);
-    }
-    PS_LAUNCH_CHECK();
-    // phase 2: finish (quadratic): stop once a sweep STARTED below 1e-4
-    if (any_big && (rc = run_phase(1e-4f, 4))) return rc;
-    // phase 3: the absolute off-norm says nothing about the small eigenvalues of a graded
-    // spectrum: sweep on while the largest SCALED off-diagonal entry is above the float32
-    // floor (well-conditioned inputs are far below it after phase 2 and skip this)
-    const float scaled_tol = opt.eigh_scaled_tol;
-    const int extra_sweeps = opt.eigh_extra_sweeps;
-    for (int extra = 0; any_big && extra <= extra_sweeps; ++extra) {
-      EStatus* slot = &status[gen % 64];
-      slot->gen = -1;
-      hipLaunchKernelGGL(eigh_scaled_off_kernel, dim3(nsq), blk, 0, st, lo.blocks, lo.sq);
-      hipLaunchKernelGGL(eigh_control_kernel, dim3(1), blk, 0, st, lo.blocks, batch, 2, scaled_tol,
-                         gen, slot);
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return (int)e;
-      if ((e = hipStreamSynchronize(st)) != hipSuccess) return (int)e;
-      if (slot->gen != gen) return PS_EINTERNAL;
-      if (opt.eigh_trace)
-        fprintf(stderr, "eigh scaled off-diagonal max %.3e, %d block(s) above %.1e\n",
-                slot->max_off, slot->active, scaled_tol);
-      ++gen;
-      if (slot->active == 0 || extra == extra_sweeps) break;
-      if ((rc = run_phase(0.f, 1))) return rc;
-    }
-    }
-    {
-      const int final_polish = opt.eigh_final_polish;
-      // the sweeps after the re-projection let V drift from orthogonality again by a few
-      // eps32 per sweep: one more Newton-Schulz step V <- V (1.5 I - 0.5 V^T V) (two products)
-      // takes most graded / rank-deficient cases to LAPACK-float32's error to three digits
-      if (final_polish && any_big && (run_two_sided || cj_polish)) {
-        if (final_polish >= 2)
-          hipLaunchKernelGGL(eigh_reproject_f64_kernel<2>, dim3(4 * nsq), blk, 0, st, lo.blocks, lo.sq);
-        else
-          hipLaunchKernelGGL((eigh_gemm_kernel<MC, MC>), dim3(nsq), blk, 0, st, lo.blocks, lo.sq, nsq,
-                             (int)GB_V, (int)GB_V, (int)GB_X, (int)GE_POLISH);
-        hipLaunchKernelGGL((eigh_gemm_kernel<KC, MC>), dim3(nsq), blk, 0, st, lo.blocks, lo.sq, nsq,
-                           (int)GB_V, (int)GB_X, (int)GB_W, (int)GE_STORE);
-        hipLaunchKernelGGL(eigh_set_active_kernel, dim3((batch + 255) / 256), blk, 0, st, lo.blocks,
-                           batch, 1);  // V <-> W
-      }
-    }
-    // One-sided path only (no small blocks, no fallback): D U is formed ONCE, float64-accumulated
-    // on the float64 MFMA as a float32 hi/lo pair; the Rayleigh quotients, and the error metric's
-    // product U^T (D U), are taken from it (39 + 8.6 ms of float64 VALU dot products and a float32
-    // D U product become 20 ms).
-    if (td_any) {   // the finish of the one-sided path (Rayleigh quotients from D V) applies to them
-      hipLaunchKernelGGL(td_mark_cj_kernel, dim3((batch + 255) / 256), blk, 0, st, lo.blocks, batch);
-      PS_LAUNCH_CHECK();
-    }
-    const bool cj_only = (cj_on || td_done) && mode == 0 && any_big && !run_two_sided &&
-                         pl.small_ids.empty() && cj_refine;
-    if (cj_only) {
-      hipLaunchKernelGGL(eigh_reproject_f64_kernel<0>, dim3(4 * nsq), blk, 0, st, lo.blocks, lo.sq);
-      hipLaunchKernelGGL(cj_rayleigh_from_dv_kernel, dim3(nsq), blk, 0, st, lo.blocks, lo.sq);
-      hipLaunchKernelGGL(eigh_scale_kernel, dim3(nsq), blk, 0, st, lo.blocks, lo.sq);
-      hipLaunchKernelGGL((eigh_gemm_kernel<KC, KC>), dim3(nsq), blk, 0, st, lo.blocks, lo.sq, nsq,
-                         (int)GB_W, (int)GB_W, (int)GB_OUT, (int)GE_SYM_STORE);
-      hipLaunchKernelGGL((eigh_gemm_kernel<MC, MC>), dim3(nsq), blk, 0, st, lo.blocks, lo.sq, nsq,
-                         (int)GB_V, (int)GB_X, (int)GB_A, (int)GE_ERR_UPPER);
-    } else {
-    {
-      const int refine = opt.eigh_refine;
-      if (refine && !pl.rq_tiles.empty() && (run_two_sided || cj_refine || !pl.small_ids.empty())) {
-        hipLaunchKernelGGL(eigh_rayleigh_f64_kernel, dim3((unsigned)pl.rq_tiles.size()), blk, 0, st,
-                           lo.blocks, lo.rq);
-        PS_LAUNCH_CHECK();
-      }
-    }
-
-    if (mode == 1) {
-      hipLaunchKernelGGL(eigh_copy_pairs_kernel, dim3(nsq), blk, 0, st, lo.blocks, lo.sq);
-      PS_LAUNCH_CHECK();
-      return PS_OK;
-    }
-    // root and error metric
-    hipLaunchKernelGGL(eigh_scale_kernel, dim3(nsq), blk, 0, st, lo.blocks, lo.sq);
-    hipLaunchKernelGGL((eigh_gemm_kernel<KC, KC>), dim3(nsq), blk, 0, st, lo.blocks, lo.sq, nsq,
-                       (int)GB_W, (int)GB_W, (int)GB_OUT, (int)GE_STORE);
-    hipLaunchKernelGGL((eigh_gemm_kernel<KC, MC>), dim3(nsq), blk, 0, st, lo.blocks, lo.sq, nsq,
-                       (int)GB_D, (int)GB_V, (int)GB_X, (int)GE_STORE);
-    hipLaunchKernelGGL((eigh_gemm_kernel<MC, MC>), dim3(nsq), blk, 0, st, lo.blocks, lo.sq, nsq,
-                       (int)GB_V, (int)GB_X, (int)GB_A, (int)GE_ERR);
-    }
-  }
-  if (mode == 1) return PS_OK;
-  hipLaunchKernelGGL(eigh_zero_out_kernel, dim3(batch, 16), blk, 0, st, lo.blocks);
-  hipLaunchKernelGGL(eigh_metrics_kernel, dim3(batch), dim3(64), 0, st, lo.blocks, batch, metrics);
-  PS_LAUNCH_CHECK();
-  return PS_OK;
+  return finish(c);
 }
 
 extern "C" int ps_eigh_root_batched_f32(void* stream, const float* const* a,
@@ -1849,7 +1870,7 @@ extern "C" int ps_eigh_root_batched_f32(void* stream, const float* const* a,
                                         float* const* out, const int32_t* ldo,
                                         float* metrics, void* workspace,
                                         size_t workspace_bytes) {
-  return eigh_driver(0, stream, a, n, lda, p, padding_start, batch, ridge_epsilon,
+  return eigh_driver(EighMode::Root, stream, a, n, lda, p, padding_start, batch, ridge_epsilon,
                      error_tolerance, relative_matrix_epsilon, out, ldo, nullptr, metrics,
                      workspace, workspace_bytes, nullptr);
 }
@@ -1862,18 +1883,19 @@ extern "C" int ps_eigh_root_batched_opt_f32(void* stream, const float* const* a,
                                             float* const* out, const int32_t* ldo,
                                             float* metrics, void* workspace,
                                             size_t workspace_bytes, const ps_options* options) {
-  return eigh_driver(0, stream, a, n, lda, p, padding_start, batch, ridge_epsilon,
+  return eigh_driver(EighMode::Root, stream, a, n, lda, p, padding_start, batch, ridge_epsilon,
                      error_tolerance, relative_matrix_epsilon, out, ldo, nullptr, metrics,
                      workspace, workspace_bytes, options);
 }
 
-extern "C" int ps_eigh_sorted_max_n(void) { return small_eigh_enabled() ? SE_MAXN : 0; }
+// largest n whose plain eigenpairs come back sorted (eigh_small_kernel)
+extern "C" int ps_eigh_sorted_max_n(void) { return SE_MAXN; }
 
 extern "C" int ps_eigh_batched_f32(void* stream, const float* const* a, const int32_t* n,
                                    const int32_t* lda, int batch, float* const* evals,
                                    float* const* evecs, const int32_t* ldv, void* workspace,
                                    size_t workspace_bytes) {
-  return eigh_driver(1, stream, a, n, lda, nullptr, nullptr, batch, 0.f, 0.f, 0, evecs, ldv,
+  return eigh_driver(EighMode::Pairs, stream, a, n, lda, nullptr, nullptr, batch, 0.f, 0.f, 0, evecs, ldv,
                      evals, nullptr, workspace, workspace_bytes, nullptr);
 }
 
@@ -1881,6 +1903,6 @@ extern "C" int ps_eigh_batched_opt_f32(void* stream, const float* const* a, cons
                                        const int32_t* lda, int batch, float* const* evals,
                                        float* const* evecs, const int32_t* ldv, void* workspace,
                                        size_t workspace_bytes, const ps_options* options) {
-  return eigh_driver(1, stream, a, n, lda, nullptr, nullptr, batch, 0.f, 0.f, 0, evecs, ldv,
+  return eigh_driver(EighMode::Pairs, stream, a, n, lda, nullptr, nullptr, batch, 0.f, 0.f, 0, evecs, ldv,
                      evals, nullptr, workspace, workspace_bytes, options);
 }

@@ -4,9 +4,9 @@
 //   D = A + ridge I (DS:1005-1006)  =  L L^T      float64-accumulated blocked Cholesky, L stored
 //                                                 as float32 in G
 //   sweeps over round-robin pairs (I, J) of 64-wide block columns of G:
-//       P = [G_I G_J]^T [G_I G_J]        128 x 128 Gram matrix        (cj_gram_kernel, MFMA f32)
+//       P = [G_I G_J]^T [G_I G_J]        128 x 128 Gram matrix        (cj_gram_x3_kernel, bf16 MFMA)
 //       Q = eigenvectors of P            one-sided Jacobi in LDS      (cj_pivot_kernel)
-//       [G_I G_J] <- [G_I G_J] Q         128-row tiles, K = 128       (cj_update_kernel, MFMA f32)
+//       [G_I G_J] <- [G_I G_J] Q         128-row tiles, K = 128       (cj_update_x6_kernel, bf16 MFMA)
 //   until every scaled Gram entry |g_i . g_j| / (|g_i| |g_j|) seen in a sweep is below `tol`.
 //   Then D = G G^T = U diag(|g_j|^2) U^T with U = the normalised columns of G: the eigenvectors
 //   need no accumulation and there is no left-side update, 6 n^3 flops per sweep instead of the
@@ -212,7 +212,7 @@ __global__ void cj_select_kernel(EighBlock* blocks, int nblocks) {
 }
 
 // ---- P = [G_I G_J]^T [G_I G_J]: one workgroup per (block, pair); the K-tile of the panel
-// (16 rows x the 128 gathered columns) is staged ONCE and serves as both MFMA operands.  P is
+// (32 rows x the 128 gathered columns) is staged ONCE and serves as both MFMA operands.  P is
 // symmetric: only the 10 upper 32 x 32 tiles (ti <= tj) are computed, dealt 3 + 3 + 2 + 2 to
 // the four wavefronts (the critical wavefront issues 3/4 of the MFMAs of the full product), and
 // only they are stored -- cj_pivot_kernel reads the upper triangle.
@@ -222,104 +222,14 @@ template <> struct GramTiles<1> { static constexpr int N = 3; static constexpr i
 template <> struct GramTiles<2> { static constexpr int N = 2; static constexpr int TI[3] = {1, 2, 0}, TJ[3] = {3, 2, 0}; };
 template <> struct GramTiles<3> { static constexpr int N = 2; static constexpr int TI[3] = {2, 3, 0}, TJ[3] = {3, 3, 0}; };
 
+// ---- the Gram matrix on the bf16 MFMA: the panel is split into three bf16 planes (x = h + l + l2) and
+// six products accumulate in float32 -- float32-level accuracy (the arithmetic of cj_update_x6_kernel)
+// at 6 / 16 of the float32 MFMA time: the kernel is HBM-bound (it streams the pair's panel once) and
+// leaves the FMA lanes to the pivots of the other stream group.  K-tile = 32 rows of the panel; every
+// thread loads a 4 x 4 patch (4 rows x 16 bytes), converts and writes it TRANSPOSED -- [column][k],
+// k-contiguous, 4 x ds_write_b64 per plane -- so that an MFMA fragment (8 consecutive k of one column)
+// is one 16-byte LDS read; rows of 40 bf16 (80 bytes) keep those reads conflict-free.
 template <int W>
-__device__ __forceinline__ void cj_gram_tiles(const float* G, int ld, const int (&goff)[2],
-                                             const int (&soff)[2], float* smem, float* P,
-                                             int lane) {
-  using T = GramTiles<W>;
-  constexpr int BK = 16, LD = SmemCfg<BK>::MC_LD;
-  f32x16 acc[T::N];
-#pragma unroll
-  for (int t = 0; t < T::N; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-  const int nk = ld / BK;
-  const int i = lane & 31, h = lane >> 5;
-  f32x4 r[2];
-#pragma unroll
-  for (int v = 0; v < 2; ++v) r[v] = gload4(G + goff[v]);
-#pragma unroll
-  for (int v = 0; v < 2; ++v) *reinterpret_cast<f32x4*>(smem + soff[v]) = r[v];
-  __syncthreads();
-  for (int kt = 0; kt < nk; ++kt) {
-    const float* cur = smem + (kt & 1) * BK * LD;
-    float* nxt = smem + ((kt + 1) & 1) * BK * LD;
-    const bool more = kt + 1 < nk;
-    if (more) {
-#pragma unroll
-      for (int v = 0; v < 2; ++v) r[v] = gload4(G + (int64_t)(kt + 1) * BK * ld + goff[v]);
-    }
-#pragma unroll
-    for (int c = 0; c < BK / 8; ++c) {
-      float f[4][4];   // fragment of column block b at k = 8c + 4h + s (unused blocks fold away)
-#pragma unroll
-      for (int b = 0; b < 4; ++b)
-#pragma unroll
-        for (int s2 = 0; s2 < 4; ++s2) f[b][s2] = cur[(8 * c + 4 * h + s2) * LD + b * 32 + i];
-#pragma unroll
-      for (int s2 = 0; s2 < 4; ++s2)
-#pragma unroll
-        for (int t = 0; t < T::N; ++t)
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(f[T::TI[t]][s2], f[T::TJ[t]][s2], acc[t],
-                                                        0, 0, 0);
-    }
-    if (more) {
-#pragma unroll
-      for (int v = 0; v < 2; ++v) *reinterpret_cast<f32x4*>(nxt + soff[v]) = r[v];
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int t = 0; t < T::N; ++t)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int row = T::TI[t] * 32 + (q & 3) + 8 * (q >> 2) + 4 * h, col = T::TJ[t] * 32 + i;
-      gstore1(P + row * JP + col, acc[t][q]);
-    }
-}
-
-__global__ __launch_bounds__(256, 2) void cj_gram_kernel(EighBlock* blocks, const ETile* tiles,
-                                                         int ntiles, int round) {
-  constexpr int BK = 16, LD = SmemCfg<BK>::MC_LD;   // [16][132]
-  __shared__ __align__(16) float smem[2 * BK * LD];
-  const ETile te = tiles[xcd_remap(blockIdx.x, ntiles)];
-  EighBlock* eb = &blocks[te.block];
-  if (!eb->cj_active || round >= eb->nb - 1) return;
-  int I, J;
-  rr_pair(eb->nb, round, te.k, I, J);
-  const int ld = eb->npad, tid = threadIdx.x;
-  const float* G = eb->X;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-  // thread -> two float4 of a K-tile: rows k = f >> 5, columns 4 * (f & 31) of the gathered panel
-  int goff[2], soff[2];
-#pragma unroll
-  for (int v = 0; v < 2; ++v) {
-    const int f = tid + 256 * v, k = f >> 5, c4 = (f & 31) * 4;
-    const int gc = c4 < JB ? I * JB + c4 : J * JB + (c4 - JB);
-    goff[v] = k * ld + gc;
-    soff[v] = k * LD + c4;
-  }
-  float* P = eb->V + (int64_t)te.k * JP * JP;
-  switch (wave) {
-    case 0: cj_gram_tiles<0>(G, ld, goff, soff, smem, P, lane); break;
-    case 1: cj_gram_tiles<1>(G, ld, goff, soff, smem, P, lane); break;
-    case 2: cj_gram_tiles<2>(G, ld, goff, soff, smem, P, lane); break;
-    default: cj_gram_tiles<3>(G, ld, goff, soff, smem, P, lane); break;
-  }
-}
-
-// ---- the same Gram matrix on the bf16 MFMA for the sweeps that are far from convergence: the panel
-// is split into bf16 hi / lo pairs (x = hi + lo) and P = hi^T hi + hi^T lo + lo^T hi accumulates in
-// float32 -- ~2^-17 relative to |g_i||g_j| per entry, i.e. scaled entries good to ~1e-5, which is
-// all a rotation needs while the largest scaled entry of the sweep is above 1e-3 (the pivot's Q is
-// orthogonal whatever P it was computed from, so G G^T = D is untouched; the STOP decision only
-// ever comes from a float32 sweep: the noise floor of this kernel is above the sweep tolerance, so
-// a block can never converge on it).  3 / 16 of the float32 MFMA time: the kernel is HBM-bound (it
-// streams the pair's panel once).  K-tile = 32 rows of the panel; every thread loads a 4 x 4
-// patch (4 rows x 16 bytes), converts and writes it TRANSPOSED -- [column][k], k-contiguous,
-// 4 x ds_write_b64 per plane -- so that an MFMA fragment (8 consecutive k of one column) is one
-// 16-byte LDS read; rows of 40 bf16 (80 bytes) keep those reads conflict-free.
-template <int W, int PLANES>
 __device__ __forceinline__ void cj_gram_x3_mfma(const uint16_t* sh, const uint16_t* sl, const uint16_t* s2,
                                                 int lane, f32x16 (&acc)[3]) {
   using T = GramTiles<W>;
@@ -331,16 +241,15 @@ __device__ __forceinline__ void cj_gram_x3_mfma(const uint16_t* sh, const uint16
     for (int b = 0; b < 4; ++b) {
       fh[b] = *reinterpret_cast<const xbf16x8*>(sh + (b * 32 + i) * XLD + ks * 16 + h8);
       fl[b] = *reinterpret_cast<const xbf16x8*>(sl + (b * 32 + i) * XLD + ks * 16 + h8);
-      if (PLANES == 3) f2[b] = *reinterpret_cast<const xbf16x8*>(s2 + (b * 32 + i) * XLD + ks * 16 + h8);
+      f2[b] = *reinterpret_cast<const xbf16x8*>(s2 + (b * 32 + i) * XLD + ks * 16 + h8);
     }
 #pragma unroll
     for (int t = 0; t < T::N; ++t) {
       f32x16 c = acc[t];
-      if (PLANES == 3) {   // the three terms of weight 2^-16: x = h + l + l2, products above 2^-24 kept
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f2[T::TI[t]], fh[T::TJ[t]], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fl[T::TI[t]], fl[T::TJ[t]], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fh[T::TI[t]], f2[T::TJ[t]], c, 0, 0, 0);
-      }
+      // first the three terms of weight 2^-16: products above 2^-24 kept
+      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f2[T::TI[t]], fh[T::TJ[t]], c, 0, 0, 0);
+      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fl[T::TI[t]], fl[T::TJ[t]], c, 0, 0, 0);
+      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fh[T::TI[t]], f2[T::TJ[t]], c, 0, 0, 0);
       c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fl[T::TI[t]], fh[T::TJ[t]], c, 0, 0, 0);
       c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fh[T::TI[t]], fl[T::TJ[t]], c, 0, 0, 0);
       c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fh[T::TI[t]], fh[T::TJ[t]], c, 0, 0, 0);
@@ -349,14 +258,10 @@ __device__ __forceinline__ void cj_gram_x3_mfma(const uint16_t* sh, const uint16
   }
 }
 
-// PLANES = 3: three bf16 planes per operand and six products -- float32-level accuracy (the
-// arithmetic of cj_update_x6_kernel), still HBM-bound: the float32 MFMA form of the Gram kernel
-// shares its FMA lanes with the pivots of the other stream group, this one does not.
-template <int PLANES>
 __global__ __launch_bounds__(256, 2) void cj_gram_x3_kernel(EighBlock* blocks, const ETile* tiles,
                                                             int ntiles, int round) {
-  // two stages x PLANES planes x [128 columns][40] bf16 = 40,960 (61,440) bytes
-  __shared__ __align__(16) uint16_t simg[2][PLANES][JP * XLD];
+  // two stages x three planes x [128 columns][40] bf16 = 61,440 bytes
+  __shared__ __align__(16) uint16_t simg[2][3][JP * XLD];
   const ETile te = tiles[xcd_remap(blockIdx.x, ntiles)];
   EighBlock* eb = &blocks[te.block];
   if (!eb->cj_active || round >= eb->nb - 1) return;
@@ -390,7 +295,7 @@ __global__ __launch_bounds__(256, 2) void cj_gram_x3_kernel(EighBlock* blocks, c
       }
       *reinterpret_cast<xbf16x4*>(&simg[stage][0][(c4 + e) * XLD + 4 * rg]) = hi;
       *reinterpret_cast<xbf16x4*>(&simg[stage][1][(c4 + e) * XLD + 4 * rg]) = lo;
-      if (PLANES == 3) *reinterpret_cast<xbf16x4*>(&simg[stage][2][(c4 + e) * XLD + 4 * rg]) = l2;
+      *reinterpret_cast<xbf16x4*>(&simg[stage][2][(c4 + e) * XLD + 4 * rg]) = l2;
     }
   };
   f32x16 acc[3];
@@ -406,10 +311,10 @@ __global__ __launch_bounds__(256, 2) void cj_gram_x3_kernel(EighBlock* blocks, c
     const bool more = kt + 1 < nk;
     if (more) load(kt + 1);
     switch (wave) {
-      case 0: cj_gram_x3_mfma<0, PLANES>(simg[cur][0], simg[cur][1], simg[cur][PLANES - 1], lane, acc); break;
-      case 1: cj_gram_x3_mfma<1, PLANES>(simg[cur][0], simg[cur][1], simg[cur][PLANES - 1], lane, acc); break;
-      case 2: cj_gram_x3_mfma<2, PLANES>(simg[cur][0], simg[cur][1], simg[cur][PLANES - 1], lane, acc); break;
-      default: cj_gram_x3_mfma<3, PLANES>(simg[cur][0], simg[cur][1], simg[cur][PLANES - 1], lane, acc); break;
+      case 0: cj_gram_x3_mfma<0>(simg[cur][0], simg[cur][1], simg[cur][2], lane, acc); break;
+      case 1: cj_gram_x3_mfma<1>(simg[cur][0], simg[cur][1], simg[cur][2], lane, acc); break;
+      case 2: cj_gram_x3_mfma<2>(simg[cur][0], simg[cur][1], simg[cur][2], lane, acc); break;
+      default: cj_gram_x3_mfma<3>(simg[cur][0], simg[cur][1], simg[cur][2], lane, acc); break;
     }
     if (more) store(cur ^ 1);
     __syncthreads();
@@ -617,51 +522,14 @@ __global__ __launch_bounds__(SE_T) void cj_pivot_kernel(EighBlock* blocks, const
   }
 }
 
-// ---- [G_I G_J] <- [G_I G_J] Q on 128-row tiles (K = 128 gathered from the two block columns)
-template <int UBK>
-__global__ __launch_bounds__(256, 2) void cj_update_kernel_t(EighBlock* blocks, const ETile* tiles,
-                                                             int ntiles, int round) {
-  __shared__ __align__(16) float smem[SmemCfg<UBK>::total(KC, MC)];
-  const ETile te = tiles[xcd_remap(blockIdx.x, ntiles)];
-  EighBlock* eb = &blocks[te.block];
-  if (!eb->cj_active || round >= eb->nb - 1) return;
-  if (reinterpret_cast<const int*>(eb->offpart)[round * eb->npairs + te.k] == 0) return;
-  int I, J;
-  rr_pair(eb->nb, round, te.k, I, J);
-  const int ld = eb->npad;
-  const float* Qg = eb->Q + (int64_t)te.k * JP * JP;
-  float* X = eb->X;
-  f32x16 acc[2][2];
-  zero_acc(acc);
-  for (int seg = 0; seg < 2; ++seg) {
-    const int cb = (seg == 0 ? I : J) * JB;
-    Operand a{X + cb, ld, te.t * TILE, ld, JB, true};         // (m,k) = X[rt+m][cb+k]
-    Operand b{Qg + seg * JB * JP, JP, 0, JP, JB, true};       // (j,k) = Q[seg*64+k][j]
-    gemm_tile_accum<KC, MC, UBK, false>(a, b, JB, smem, acc);
-  }
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int wm = wave >> 1, wn = wave & 1;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = te.t * TILE + acc_row(wm, i, r, lane);
-        const int c = acc_col(wn, j, lane);
-        const int col = c < JB ? I * JB + c : J * JB + (c - JB);
-        gstore1(X + (int64_t)row * ld + col, acc[i][j][r]);
-      }
-}
-
-// ---- the same update on the bf16 MFMA: both operands split three ways (gemm_bf16x.hip.h), six
-// partial products per product, float32 accumulation: ~2^-22 relative per product -- the size of
-// the float32 chain's own rounding at K = 128 -- at 6 / 16 of the float32 MFMA time, which turns
-// the update from an MFMA-bound into an HBM-bound kernel (it reads and writes G once per round)
-// and leaves the shared VALU / MFMA pipe to the pivot kernel of the other stream group.  The
-// rotation Q is orthogonal to float32 accuracy whatever the arithmetic of its application, so
-// G G^T = D holds to the product's rounding as before; the convergence test stays on the float32
-// Gram kernel.  Q arrives transposed (cj_pivot_kernel store_transposed): Q^T[c][k].
+// ---- [G_I G_J] <- [G_I G_J] Q on 128-row tiles (K = 128 gathered from the two block columns) on the
+// bf16 MFMA: both operands split three ways (gemm_bf16x.hip.h), six partial products per product,
+// float32 accumulation: ~2^-22 relative per product -- the size of a float32 chain's own rounding at
+// K = 128 -- at 6 / 16 of the float32 MFMA time, which makes the update an HBM-bound kernel (it reads
+// and writes G once per round) and leaves the shared VALU / MFMA pipe to the pivot kernel of the other
+// stream group.  The rotation Q is orthogonal to float32 accuracy whatever the arithmetic of its
+// application, so G G^T = D holds to the product's rounding.  Q arrives transposed (cj_pivot_kernel
+// store_transposed): Q^T[c][k].
 __global__ __launch_bounds__(256, 2) void cj_update_x6_kernel(EighBlock* blocks, const ETile* tiles,
                                                               int ntiles, int round) {
   extern __shared__ __align__(16) float smem_x6[];   // 6 planes of 128 x 40 bf16 = 61,440 bytes

@@ -26,6 +26,7 @@ namespace psk {
 constexpr int TD_NB = 32;     // panel width of the reduction
 constexpr int TD_KB = 128;    // reflectors per WY block of the back-transformation
 constexpr int TD_MAXN = 4096; // the deflation kernel keeps a merge problem in LDS
+constexpr float TD_DEFL_EPS = 1e-8f;  // deflation tolerance of the divide and conquer (x 8 ||T||)
 constexpr int TD_TAIL = 192;  // the last <= 192 columns of a block are reduced inside LDS by one workgroup
 static_assert(TD_TAIL <= 192, "td_tail_kernel: one thread per row, three 64-column strips, 160 KB of LDS");
 

@@ -38,38 +38,14 @@ void ps_dev_env_overrides(Options& o) {
   geti("PS_NEWTON_STAGGER", o.stagger);
   o.newton_prof = getenv("PS_NEWTON_PROF") != nullptr;
   o.newton_trace = getenv("PS_NEWTON_TRACE");
-  geti("PS_EIGH_SMALL", o.eigh_small);
-  geti("PS_EIGH_SMALL_REFRESH", o.eigh_small_refresh);
   o.eigh_trace = getenv("PS_EIGH_TRACE") != nullptr;
   geti("PS_EIGH_CJ", o.eigh_cj);
   geti("PS_EIGH_CJ_REFINE", o.eigh_cj_refine);
-  geti("PS_EIGH_CJ_POLISH", o.eigh_cj_polish);
-  getf("PS_EIGH_CJ_TOL", o.eigh_sweep_tol);
-  geti("PS_EIGH_CJ_INNER", o.eigh_cj_inner);
-  getf("PS_EIGH_CJ_DONE", o.eigh_cj_done);
-  geti("PS_EIGH_CJ_MAX_SWEEPS", o.eigh_cj_max_sweeps);
-  geti("PS_EIGH_CJ_STATIONARY", o.eigh_cj_stationary);
-  getf("PS_EIGH_CJ_ONE_BELOW", o.eigh_cj_one_below);
-  geti("PS_EIGH_CJ_SORT", o.eigh_cj_sort);
-  geti("PS_EIGH_CJ_STREAMS", o.eigh_streams);
-  geti("PS_EIGH_CJ_UBK", o.eigh_cj_ubk);
-  geti("PS_EIGH_UPDATE_X6", o.eigh_update_bf16x6);
-  geti("PS_EIGH_GRAM_X6", o.eigh_gram_bf16x6);
-  getf("PS_EIGH_GRAM_X3", o.eigh_gram_x3_above);
-  getf("PS_EIGH_GRAM_X3_SKIP", o.eigh_gram_x3_skip);
-  geti("PS_EIGH_F64_REPROJECT", o.eigh_f64_reproject);
-  getf("PS_EIGH_SCALED_TOL", o.eigh_scaled_tol);
-  geti("PS_EIGH_EXTRA_SWEEPS", o.eigh_extra_sweeps);
-  geti("PS_EIGH_FINAL_POLISH", o.eigh_final_polish);
   geti("PS_EIGH_REFINE", o.eigh_refine);
   geti("PS_EIGH_TD", o.eigh_td);
   geti("PS_EIGH_TD_STAGE", o.eigh_td_stage);
-  getf("PS_EIGH_TD_DEFL_EPS", o.eigh_td_defl_eps);
   geti("PS_EIGH_TD_STREAMS", o.eigh_td_streams);
   geti("PS_EIGH_TD_TAIL", o.eigh_td_tail);
-  getf("PS_EIGH_TD_MAX_COND", o.eigh_td_max_cond);
-  geti("PS_EIGH_TD_FORCE", o.eigh_td_force);
-  geti("PS_EIGH_TD_ACCURATE", o.eigh_td_accurate);
   geti("PS_QUANT_FLAT", o.quant_flat);
   geti("PS_QUANT_STRIP", o.quant_strip);
   geti("PS_FD_GROUPS", o.fd_groups);

@@ -192,14 +192,13 @@ def test_eigh_root_two_sided_fallback_for_indefinite_input(device, monkeypatch):
   assert torch.allclose(roots[1], roots2[1], rtol=0, atol=2e-4 * float(roots2[1].abs().max()))
 
 
-def test_eigh_root_one_stream_and_two_streams_agree(device, monkeypatch):
+def test_eigh_root_one_stream_and_two_streams_agree(device):
   """The two stream groups sweep disjoint blocks: results do not depend on the interleaving."""
   mats = [torch.tensor(wishart(256 + 128 * (i % 2), 1024, 40 + i), device=device) for i in range(5)]
-  one = {"eigh_solver": "one_sided"}
-  monkeypatch.setenv("PS_EIGH_CJ_STREAMS", "1")
-  r1, m1 = K().matrix_inverse_pth_root_batched(mats, [2] * 5, eigh=True, options=one)
-  monkeypatch.setenv("PS_EIGH_CJ_STREAMS", "2")
-  r2, m2 = K().matrix_inverse_pth_root_batched(mats, [2] * 5, eigh=True, options=one)
+  r1, m1 = K().matrix_inverse_pth_root_batched(mats, [2] * 5, eigh=True,
+                                               options={"eigh_solver": "one_sided", "eigh_streams": 1})
+  r2, m2 = K().matrix_inverse_pth_root_batched(mats, [2] * 5, eigh=True,
+                                               options={"eigh_solver": "one_sided", "eigh_streams": 2})
   for a, b in zip(r1, r2):
     assert torch.equal(a, b)
   assert torch.equal(m1, m2)

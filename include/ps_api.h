@@ -785,6 +785,19 @@ typedef struct {
 int ps_fd_block_columns(int rank, int d);
 size_t ps_fd_update_workspace_bytes(const ps_fd_update_desc* d);   /* 0 = unsupported shape */
 int ps_fd_update_batched_f32(void* stream, const ps_fd_update_desc* d, int32_t* info_host);
+/* The two launch-only halves of ps_fd_update_batched_f32 around its iteration (the update calls exactly these):
+ *   ps_fd_prepare_f32: weighted[j] ([d][rank]) = sketch_j * sqrt(eigs_j + ridge_j) from the packed prev
+ *     [batch][d][rank + 2]; ridge_j = ridge_epsilon * max(relative ? eigs_j[0] : 1, error_tolerance).
+ *   ps_fd_finish_f32: DS:1196-1290 and the packing from the Ritz values theta [batch][b] (descending; the
+ *     leading rank + 1 are used) and Ritz vectors x [batch][d][b] (the leading rank columns) -> out
+ *     [batch][d][rank + 2].  scratch: ps_fd_finish_scratch_bytes(batch, rank) = batch * 32 * rank floats.
+ * Any d, b, rank with rank + 1 <= b and rank + 2 < d (PS_EINVAL otherwise, and for NULLs); ps_fd_finish_f32
+ * returns PS_EUNSUPPORTED where 5 rank + 1 floats exceed 48 KiB of LDS.  Only enqueue. */
+int ps_fd_prepare_f32(void* stream, const float* prev, float* weighted, int batch, int d, int rank,
+                      float ridge_epsilon, float error_tolerance, int relative);
+size_t ps_fd_finish_scratch_bytes(int batch, int rank);
+int ps_fd_finish_f32(void* stream, const float* theta, const float* x, const float* prev, float* scratch,
+                     float* out, int batch, int d, int b, int rank, int p, float decay);
 int ps_chol_rinv_max_n(void);
 int ps_chol_rinv_batched_f32(void* stream, const float* gram, float* out, int b, int batch,
                              float drop_rel);

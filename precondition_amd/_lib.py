@@ -325,6 +325,12 @@ _SIGNATURES = {
     "ps_fd_block_columns": (C.c_int, [C.c_int, C.c_int]),
     "ps_fd_update_workspace_bytes": (C.c_size_t, [C.POINTER(FdUpdateDesc)]),
     "ps_fd_update_batched_f32": (C.c_int, [C.c_void_p, C.POINTER(FdUpdateDesc), C.c_void_p]),
+    "ps_fd_prepare_f32":
+        (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int]),
+    "ps_fd_finish_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "ps_fd_finish_f32":
+        (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                   C.c_int, C.c_int, C.c_int, C.c_float]),
     "ps_chol_rinv_max_n": (C.c_int, []),
     "ps_chol_rinv_batched_f32":
         (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float]),

@@ -246,6 +246,39 @@ using namespace psk;
 
 extern "C" int ps_fd_block_columns(int rank, int d) { return fd_block_columns(rank, d); }
 
+// The two launch-only halves around the iteration, as entry points of their own: fd_run_begin / fd_run_finish call
+// them, so what a test of them sees is what an update runs.  Every shape the kernels are written for is accepted
+// (the d % 128 == 0 domain is the iteration's, not theirs).
+extern "C" int ps_fd_prepare_f32(void* stream, const float* prev, float* weighted, int batch, int d, int rank,
+                                 float ridge_epsilon, float error_tolerance, int relative) {
+  PS_DEVICE_CHECK();
+  if (!prev || !weighted || batch < 1 || batch > 65535 || d < 1 || rank < 1 || rank + 2 >= d) return PS_EINVAL;
+  hipLaunchKernelGGL(fd_prep_kernel, dim3(64, batch), dim3(256), 0, (hipStream_t)stream, prev, weighted, d, rank,
+                     ridge_epsilon, error_tolerance, relative);
+  PS_LAUNCH_CHECK();
+  return PS_OK;
+}
+
+extern "C" size_t ps_fd_finish_scratch_bytes(int batch, int rank) {
+  return batch < 1 || rank < 1 ? 0 : (size_t)batch * FD_NP * (size_t)rank * sizeof(float);
+}
+
+extern "C" int ps_fd_finish_f32(void* stream, const float* theta, const float* x, const float* prev, float* scratch,
+                                float* out, int batch, int d, int b, int rank, int p, float decay) {
+  PS_DEVICE_CHECK();
+  if (!theta || !x || !prev || !scratch || !out || batch < 1 || batch > 65535 || d < 1 || rank < 1 || p < 1 ||
+      rank + 1 > b || rank + 2 >= d)
+    return PS_EINVAL;
+  const size_t lds = (size_t)((rank + 1) + 4 * rank) * sizeof(float);
+  if (lds > 48 * 1024) return PS_EUNSUPPORTED;   // the O(rank) scalars of a factor live in LDS (rank <= 2457)
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(fd_colnorm_part_kernel, dim3(FD_NP, batch), dim3(256), 0, st, x, scratch, d, b, rank);
+  hipLaunchKernelGGL(fd_finish_kernel, dim3(FD_NS, batch), dim3(256), lds, st, theta, x, prev, scratch, out, d, b,
+                     rank, p, decay);
+  PS_LAUNCH_CHECK();
+  return PS_OK;
+}
+
 static int fd_update_supported(const ps_fd_update_desc* u, int* b_out) {
   if (!u || u->batch < 1 || u->d < 1 || u->rank < 1 || u->p < 1) return PS_EINVAL;
   const int B = u->batch, d = u->d, r = u->rank, b = fd_block_columns(r, d);
@@ -328,9 +361,8 @@ int fd_run_begin(FdRun& g, void* workspace, size_t workspace_bytes) {
   fd_descs(g.ds, w, B, d, r, b);
 
   // ---- prepare: C = sym(decay W W^T + Gram), bf16 planes ----------------------------------------
-  hipLaunchKernelGGL(fd_prep_kernel, dim3(64, B), dim3(256), 0, st, u->prev, w.weighted, d, r, u->ridge_epsilon,
-                     u->error_tolerance, u->relative_matrix_epsilon);
-  PS_LAUNCH_CHECK();
+  PS_RC(ps_fd_prepare_f32(stream, u->prev, w.weighted, B, d, r, u->ridge_epsilon, u->error_tolerance,
+                          u->relative_matrix_epsilon));
   PS_RC(ps_gemm_grouped_f32(stream, g.ds[8].data(), B, w.plan_ws[8], w.plan_ws_bytes[8]));
   std::vector<const float*> grams(B);
   if (u->input_is_factor) {   // Gram = R R^T (the reference's statistics slot holds R, DS:1497-1505)
@@ -409,11 +441,7 @@ int fd_run_finish(FdRun& g) {
   const int B = u->batch, d = u->d, r = u->rank, b = g.b;
   FdCarve& w = g.w;
   // (w.tmp, the rounds' [B][d][b] temporary, is free now: the column norms' partial sums go there)
-  hipLaunchKernelGGL(fd_colnorm_part_kernel, dim3(FD_NP, B), dim3(256), 0, g.st, w.x, w.tmp, d, b, r);
-  const size_t lds = (size_t)((r + 1) + 4 * r) * sizeof(float);
-  hipLaunchKernelGGL(fd_finish_kernel, dim3(FD_NS, B), dim3(256), lds, g.st, w.theta, w.x, u->prev, w.tmp, u->out, d, b,
-                     r, u->p, u->decay);
-  PS_LAUNCH_CHECK();
+  PS_RC(ps_fd_finish_f32((void*)g.st, w.theta, w.x, u->prev, w.tmp, u->out, B, d, b, r, u->p, u->decay));
   PS_HIP(hipMemcpyAsync(u->converged, w.conv, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, g.st));
   return PS_OK;
 }

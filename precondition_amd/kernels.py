@@ -1050,6 +1050,45 @@ def fd_update_batched(new_grads, prev, p, rank, decay, ridge_epsilon, error_tole
   return out, conv, {"outer_iterations": int(info[0]), "filter_products": int(info[1]), "block": int(info[2])}
 
 
+@_device_guarded
+def fd_prepare(prev, rank, ridge_epsilon, error_tolerance, relative_matrix_epsilon, out=None):
+  """W_j = sketch_j * sqrt(eigs_j + ridge_j) of the packed sketches prev [B, d, rank + 2] (ps_fd_prepare_f32, the
+  first step of ps_fd_update_batched_f32; DS:1160-1172).  Returns [B, d, rank] (or fills `out`)."""
+  _require_gpu(prev, "fd_prepare")
+  if prev.dim() != 3 or prev.shape[2] != rank + 2 or not prev.is_contiguous() or prev.dtype != torch.float32:
+    raise ValueError("fd_prepare expects a contiguous float32 [B, d, rank + 2] tensor")
+  bsz, d = int(prev.shape[0]), int(prev.shape[1])
+  if out is None:
+    out = torch.empty((bsz, d, rank), dtype=torch.float32, device=prev.device)
+  elif tuple(out.shape) != (bsz, d, rank) or not out.is_contiguous() or out.dtype != torch.float32:
+    raise ValueError("fd_prepare: out must be a contiguous float32 [B, d, rank] tensor")
+  check(lib().ps_fd_prepare_f32(_stream(), prev.data_ptr(), out.data_ptr(), bsz, d, int(rank), float(ridge_epsilon),
+                                float(error_tolerance), int(bool(relative_matrix_epsilon))), "ps_fd_prepare_f32")
+  return out
+
+
+@_device_guarded
+def fd_finish(theta, x, prev, p, rank, decay, out=None):
+  """DS:1196-1290 and the packing (ps_fd_finish_f32, the last step of ps_fd_update_batched_f32): theta [B, b]
+  descending Ritz values, x [B, d, b] Ritz vectors, prev [B, d, rank + 2] -> packed [B, d, rank + 2]."""
+  for t in (theta, x, prev):
+    _require_gpu(t, "fd_finish")
+    if not t.is_contiguous() or t.dtype != torch.float32:
+      raise ValueError("fd_finish expects contiguous float32 tensors")
+  bsz, d, b = (int(v) for v in x.shape)
+  if tuple(theta.shape) != (bsz, b) or tuple(prev.shape) != (bsz, d, rank + 2):
+    raise ValueError("fd_finish: shape mismatch")
+  if out is None:
+    out = torch.empty((bsz, d, rank + 2), dtype=torch.float32, device=x.device)
+  elif tuple(out.shape) != (bsz, d, rank + 2) or not out.is_contiguous() or out.dtype != torch.float32:
+    raise ValueError("fd_finish: out must be a contiguous float32 [B, d, rank + 2] tensor")
+  L = lib()
+  scratch = _workspace(max(int(L.ps_fd_finish_scratch_bytes(bsz, int(rank))), 256), x.device)
+  check(L.ps_fd_finish_f32(_stream(), theta.data_ptr(), x.data_ptr(), prev.data_ptr(), scratch.data_ptr(),
+                           out.data_ptr(), bsz, d, b, int(rank), int(p), float(decay)), "ps_fd_finish_f32")
+  return out
+
+
 def fd_update_root(*args, **kwargs):
   from . import low_rank
   return low_rank._fd_update_root(*args, **kwargs)

@@ -480,6 +480,48 @@ int ps_gemm_grouped_typed(void* stream, const ps_gemm_desc* desc, int count,
                           int a_dtype, int b_dtype,
                           void* workspace, size_t workspace_bytes);
 
+/* Grouped product with SEGMENTED rows: the application of the preconditioners to a rank-3 block.
+ * For a block [a,b,c] cut from a row-major parameter [A,B,C] the reference contracts the leading
+ * axis three times, each result carrying the new axis last (DS:1689-1708):
+ *     X1[(b c), a']  = G [a,(b c)]^T  P_a    A = the block in place, lda = B*C, transa = 1
+ *     X2[(c a'),b']  = X1[b,(c a')]^T P_b    contiguous scratch on both sides
+ *     Y [(a' b'),c'] = X2[c,(a' b')]^T P_c   written into the output parameter, ldc = C
+ * Row (b,c) of the first product's operand A lies at b*C + c: b_n segments of c_n rows, C elements
+ * apart; row (a',b') of the last product's result lies at a'*B*C + b'*C: a_n segments of b_n rows,
+ * B*C elements apart.  Both are plain matrices only when the block spans the whole axis.
+ *
+ * ps_gemm_seg_desc is ps_gemm_desc plus that split of the row index m of op(A) and of C:
+ *   m_seg          rows per segment; 0 or m: unsegmented (the descriptor then means exactly what the
+ *                  ps_gemm_desc of its leading fields means).  Otherwise m must be a multiple of m_seg.
+ *   a_seg_stride   elements (of A's storage type) between the first rows of consecutive segments of A;
+ *                  row r of op(A), element kk: a[(r / m_seg)*a_seg_stride + kk*lda + r % m_seg]
+ *                  (transa = 1; lda >= m_seg).  A segmented descriptor with transa = 0 is
+ *                  PS_EUNSUPPORTED.
+ *   c_seg_stride   elements between the first rows of consecutive segments of C:
+ *                  c[(r / m_seg)*c_seg_stride + (r % m_seg)*ldc + col].
+ * B is never segmented.  A tile never straddles a segment: a descriptor is cut into
+ * (m / m_seg) * ceil(m_seg / 128) * ceil(n / 128) tiles; one whose tile coordinates exceed 32767 is
+ * PS_EUNSUPPORTED.  Storage types: F32 / F32 in any orientation, BF16 A with transa = 1, transb = 0;
+ * everything else PS_EUNSUPPORTED.  A call that returns an error has launched and written nothing.
+ * Every element sums its products in the k order of ps_gemm_grouped_typed (split-K chosen by the
+ * same rule on this call's tile count), so an unsegmented run on a contiguous copy of the operands
+ * gives the same bits whenever neither call splits k. */
+typedef struct {
+  const float* a;
+  const float* b;
+  float* c;
+  int32_t m, n, k;
+  int32_t transa, transb;
+  int64_t lda, ldb, ldc;
+  int32_t m_seg;
+  int64_t a_seg_stride, c_seg_stride;
+} ps_gemm_seg_desc;
+
+size_t ps_gemm_grouped_seg_workspace_bytes(const ps_gemm_seg_desc* desc, int count);
+int ps_gemm_grouped_seg_typed(void* stream, const ps_gemm_seg_desc* desc, int count,
+                              int a_dtype, int b_dtype,
+                              void* workspace, size_t workspace_bytes);
+
 /* The same grouped product as a reusable plan: the task / tile tables are built and uploaded into
  * the caller's workspace once (create), and every launch is one or two kernel launches with no
  * host-side table building.  The operand POINTERS, shapes and the workspace must stay unchanged

@@ -47,6 +47,13 @@ class GemmDesc(C.Structure):
   ]
 
 
+class GemmSegDesc(C.Structure):
+  """Mirror of ps_gemm_seg_desc: ps_gemm_desc plus the split of the row index m."""
+  _fields_ = GemmDesc._fields_ + [
+      ("m_seg", C.c_int32), ("a_seg_stride", C.c_int64), ("c_seg_stride", C.c_int64),
+  ]
+
+
 class GemmBf16Desc(C.Structure):
   """Mirror of ps_gemm_bf16_desc."""
   _fields_ = [("a_hi", C.c_void_p), ("a_lo", C.c_void_p), ("b_hi", C.c_void_p),
@@ -263,6 +270,10 @@ _SIGNATURES = {
         (C.c_int, [C.c_void_p, C.POINTER(GemmDesc), C.c_int, C.c_void_p, C.c_size_t]),
     "ps_gemm_grouped_typed":
         (C.c_int, [C.c_void_p, C.POINTER(GemmDesc), C.c_int, C.c_int, C.c_int, C.c_void_p,
+                   C.c_size_t]),
+    "ps_gemm_grouped_seg_workspace_bytes": (C.c_size_t, [C.POINTER(GemmSegDesc), C.c_int]),
+    "ps_gemm_grouped_seg_typed":
+        (C.c_int, [C.c_void_p, C.POINTER(GemmSegDesc), C.c_int, C.c_int, C.c_int, C.c_void_p,
                    C.c_size_t]),
     "ps_gemm_grouped_plan_create":
         (C.c_int, [C.c_void_p, C.POINTER(GemmDesc), C.c_int, C.c_void_p, C.c_size_t,

@@ -133,7 +133,12 @@ struct GTask {
   int m, n, k, lda, ldb, ldc, veca, vecb;
   int ksplit, kchunk;   // split-K: tile (tm, tn, ks) covers k in [ks*kchunk, (ks+1)*kchunk)
   float* partial;       // [ksplit][m][n] when ksplit > 1
+  // segmented rows (ps_gemm_seg_desc; read by gemm_grouped_seg_kernel only): rows per segment,
+  // tile rows per segment, elements between the segments of A and of C
+  int m_seg, seg_tm;
+  int64_t a_seg, c_seg;
 };
+// tm counts tile rows across the segments of a segmented task: segment tm / seg_tm, row tm % seg_tm
 struct GTile { int task; short tm, tn; int ks; };
 
 // One-row products (m = 1: the preconditioner applied to a vector block, g^T P) are a
@@ -200,24 +205,21 @@ constexpr int GEMM_GROUPED_LDS_BYTES = SmemCfg<GBK_FAST>::TOTAL * (int)sizeof(fl
 // AH / BH: that operand is stored as bf16 (ps_gemm_grouped_typed).  GTask::a / b then address
 // 2-byte elements and veca / vecb mean "8-byte loads of four elements are legal"; the tile loader
 // widens into the float32 kernel's LDS image (gemm_core.hip.h), everything else is shared.
-template <int LA, int LB, bool AH = false, bool BH = false>
-__global__ __launch_bounds__(256, 2) void gemm_grouped_kernel(const GTask* tasks,
-                                                              const GTile* tiles, int ntiles) {
+// One tile of a task.  a / m: operand A and its row count -- the task's own, or one segment of them
+// (gemm_grouped_seg_kernel); te.tm counts tile rows inside [0, m); out / ldo: where row 0 of those m
+// rows is written (c, or the split's partial product).
+template <int LA, int LB, bool AH, bool BH>
+__device__ __forceinline__ void grouped_tile(const GTask& tk, const GTile& te, const storage_t<AH>* a,
+                                             int m, float* out, int ldo, float* smem) {
   static_assert(!(AH && BH), "at most one bf16 operand");
-  extern __shared__ __align__(16) float smem[];
-  const GTile te = tiles[blockIdx.x];   // dispatch order (common.h deal_to_xcds)
-  if (te.task < 0) return;
-  const GTask tk = tasks[te.task];
   const int k0 = te.ks * tk.kchunk;
   const int kext = min(tk.kchunk, tk.k - k0);
   // element (mn, k) of a KC operand lies at p[mn*ld + k], of an MC operand at p[k*ld + mn]
-  const storage_t<AH>* ap = (const storage_t<AH>*)tk.a + (LA == KC ? (int64_t)k0 : (int64_t)k0 * tk.lda);
+  const storage_t<AH>* ap = a + (LA == KC ? (int64_t)k0 : (int64_t)k0 * tk.lda);
   const storage_t<BH>* bp = (const storage_t<BH>*)tk.b + (LB == KC ? (int64_t)k0 : (int64_t)k0 * tk.ldb);
-  OperandT<storage_t<AH>> A{ap, tk.lda, te.tm * TILE, tk.m, kext, tk.veca != 0};
+  OperandT<storage_t<AH>> A{ap, tk.lda, te.tm * TILE, m, kext, tk.veca != 0};
   OperandT<storage_t<BH>> B{bp, tk.ldb, te.tn * TILE, tk.n, kext, tk.vecb != 0};
   f32x16 acc[2][2];
-  float* out = tk.ksplit > 1 ? tk.partial + (int64_t)te.ks * tk.m * tk.n : tk.c;
-  const int ldo = tk.ksplit > 1 ? tk.n : tk.ldc;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
@@ -227,7 +229,7 @@ __global__ __launch_bounds__(256, 2) void gemm_grouped_kernel(const GTask* tasks
     return;
   }
   const bool fast = tk.veca != 0 && tk.vecb != 0 && kext % GBK_FAST == 0 &&
-                    (te.tm + 1) * TILE <= tk.m && (te.tn + 1) * TILE <= tk.n;
+                    (te.tm + 1) * TILE <= m && (te.tn + 1) * TILE <= tk.n;
   if (fast) {
     gemm_tile<LA, LB, GBK_FAST, false, true>(A, B, kext, smem, acc);
     const int lane_off = 4 * (lane >> 5) * ldo + (lane & 31);
@@ -252,14 +254,49 @@ __global__ __launch_bounds__(256, 2) void gemm_grouped_kernel(const GTask* tasks
       for (int r = 0; r < 16; ++r) {
         const int row = te.tm * TILE + acc_row(wm, i, r, lane);
         const int col = te.tn * TILE + acc_col(wn, j, lane);
-        if (row < tk.m && col < tk.n) gstore1(out + (int64_t)row * ldo + col, acc[i][j][r]);
+        if (row < m && col < tk.n) gstore1(out + (int64_t)row * ldo + col, acc[i][j][r]);
       }
 }
 
+template <int LA, int LB, bool AH = false, bool BH = false>
+__global__ __launch_bounds__(256, 2) void gemm_grouped_kernel(const GTask* tasks,
+                                                              const GTile* tiles, int ntiles) {
+  extern __shared__ __align__(16) float smem[];
+  const GTile te = tiles[blockIdx.x];   // dispatch order (common.h deal_to_xcds)
+  if (te.task < 0) return;
+  const GTask tk = tasks[te.task];
+  float* out = tk.ksplit > 1 ? tk.partial + (int64_t)te.ks * tk.m * tk.n : tk.c;
+  const int ldo = tk.ksplit > 1 ? tk.n : tk.ldc;
+  grouped_tile<LA, LB, AH, BH>(tk, te, (const storage_t<AH>*)tk.a, tk.m, out, ldo, smem);
+}
+
+// The same tiles on tasks with segmented rows (ps_gemm_seg_desc; DS:1689-1708 on a rank-3 block in
+// place): the m rows of op(A) and of C are m / m_seg runs of m_seg rows, a_seg / c_seg elements
+// apart.  A tile lies inside one segment, so below the two base addresses it is the tile of an
+// m_seg-row task: same loads, same k order, same bits as gemm_grouped_kernel on a contiguous copy.
+// Unsegmented tasks are one segment (m_seg = m).
+template <int LA, int LB, bool AH = false>
+__global__ __launch_bounds__(256, 2) void gemm_grouped_seg_kernel(const GTask* tasks,
+                                                                  const GTile* tiles, int ntiles) {
+  extern __shared__ __align__(16) float smem[];
+  GTile te = tiles[blockIdx.x];
+  if (te.task < 0) return;
+  const GTask tk = tasks[te.task];
+  const int seg = te.tm / tk.seg_tm;
+  te.tm = (short)(te.tm - seg * tk.seg_tm);
+  // a split's partial product is the whole [m][n] result, contiguous: segment seg starts at row seg*m_seg
+  float* out = tk.ksplit > 1
+                   ? tk.partial + ((int64_t)te.ks * tk.m + (int64_t)seg * tk.m_seg) * tk.n
+                   : tk.c + seg * tk.c_seg;
+  const int ldo = tk.ksplit > 1 ? tk.n : tk.ldc;
+  grouped_tile<LA, LB, AH, false>(tk, te, (const storage_t<AH>*)tk.a + seg * tk.a_seg, tk.m_seg, out,
+                                  ldo, smem);
+}
+
 // c = sum over the K splits of the partial products, in split order (deterministic).
-__global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(const GTask* tasks,
-                                                                 const int* task_ids) {
-  const GTask tk = tasks[task_ids[blockIdx.x]];
+// SEG: c's rows are segmented (GTask::m_seg, c_seg).
+template <bool SEG>
+__device__ __forceinline__ void splitk_reduce(const GTask& tk) {
   const int64_t mn = (int64_t)tk.m * tk.n;
   for (int64_t e = blockIdx.y * 256 + threadIdx.x; e < mn; e += (int64_t)gridDim.y * 256) {
     // all partials of the element in flight, then summed in split order (deterministic)
@@ -271,8 +308,18 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(const GTask* ta
       v = (((v + p0) + p1) + p2) + p3;
     }
     for (; s < tk.ksplit; ++s) v += tk.partial[s * mn + e];
-    tk.c[(e / tk.n) * tk.ldc + e % tk.n] = v;
+    const int64_t row = e / tk.n;
+    if (SEG) tk.c[(row / tk.m_seg) * tk.c_seg + (row % tk.m_seg) * tk.ldc + e % tk.n] = v;
+    else tk.c[row * tk.ldc + e % tk.n] = v;
   }
+}
+__global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(const GTask* tasks,
+                                                                 const int* task_ids) {
+  splitk_reduce<false>(tasks[task_ids[blockIdx.x]]);
+}
+__global__ __launch_bounds__(256) void gemm_splitk_reduce_seg_kernel(const GTask* tasks,
+                                                                     const int* task_ids) {
+  splitk_reduce<true>(tasks[task_ids[blockIdx.x]]);
 }
 }  // namespace psk
 
@@ -290,19 +337,34 @@ static int splitk_for(int total_tiles, int k) {
   return std::max(1, std::min(s, 64));
 }
 
-static size_t grouped_total_tiles(const ps_gemm_desc* d, int count) {
+// Rows per segment of a descriptor (one segment of m rows unless it is a segmented ps_gemm_seg_desc;
+// a value that does not divide m is rejected by gplan_build) and its tile rows: a tile never
+// straddles a segment.
+static int desc_m_seg(const ps_gemm_desc& d) { return d.m; }
+static int desc_m_seg(const ps_gemm_seg_desc& d) {
+  return d.m_seg > 0 && d.m_seg < d.m && d.m % d.m_seg == 0 ? d.m_seg : d.m;
+}
+template <class Desc>
+static size_t desc_tiles_m(const Desc& d) {
+  const int ms = std::max(desc_m_seg(d), 1);
+  return (size_t)(d.m / ms) * ((ms + TILE - 1) / TILE);
+}
+
+template <class Desc>
+static size_t grouped_total_tiles(const Desc* d, int count) {
   size_t tiles = 0;
   for (int i = 0; i < count; ++i)
-    tiles += (size_t)((d[i].m + TILE - 1) / TILE) * ((d[i].n + TILE - 1) / TILE);
+    tiles += desc_tiles_m(d[i]) * ((d[i].n + TILE - 1) / TILE);
   return tiles;
 }
 
-static size_t grouped_gemm_bytes(const ps_gemm_desc* d, int count) {
+template <class Desc>
+static size_t grouped_gemm_bytes(const Desc* d, int count) {
   const size_t tiles = grouped_total_tiles(d, count);
   size_t split_tiles = 0, partial = 0;
   for (int i = 0; i < count; ++i) {
     const int s = splitk_for((int)std::min<size_t>(tiles, 1 << 30), d[i].k);
-    split_tiles += (size_t)s * ((d[i].m + TILE - 1) / TILE) * ((d[i].n + TILE - 1) / TILE);
+    split_tiles += (size_t)s * desc_tiles_m(d[i]) * ((d[i].n + TILE - 1) / TILE);
     if (s > 1) partial += psh::align_up((size_t)s * d[i].m * d[i].n * sizeof(float), 256) + 256;
   }
   return 4 * (psh::align_up(sizeof(GTask) * count, 256) + 256) +
@@ -311,6 +373,11 @@ static size_t grouped_gemm_bytes(const ps_gemm_desc* d, int count) {
 }
 
 extern "C" size_t ps_gemm_grouped_workspace_bytes(const ps_gemm_desc* desc, int count) {
+  if (!desc || count <= 0) return 0;
+  return grouped_gemm_bytes(desc, count);
+}
+
+extern "C" size_t ps_gemm_grouped_seg_workspace_bytes(const ps_gemm_seg_desc* desc, int count) {
   if (!desc || count <= 0) return 0;
   return grouped_gemm_bytes(desc, count);
 }
@@ -326,20 +393,43 @@ struct ps_gemm_plan {
   int* di[4] = {nullptr, nullptr, nullptr, nullptr};
   int ntiles[4] = {0, 0, 0, 0}, nsplit[4] = {0, 0, 0, 0};
   int a_dtype = PS_DTYPE_F32, b_dtype = PS_DTYPE_F32;   // storage of the operands (ps_gemm_grouped_typed)
+  bool seg = false;   // built from ps_gemm_seg_desc: launched as gemm_grouped_seg_kernel
 };
 
 // 8-byte loads of four bf16 elements
 static bool vec_ok_h(const void* p, int ld) { return ((uintptr_t)p % 8 == 0) && (ld % 4 == 0); }
 
-static int gplan_build(hipStream_t st, const ps_gemm_desc* desc, int count, void* workspace,
+// The segment fields of a task: none for a ps_gemm_desc (one segment of m rows).
+static int task_segments(const ps_gemm_desc& d, GTask& t) {
+  t.m_seg = d.m;
+  t.seg_tm = (d.m + TILE - 1) / TILE;
+  t.a_seg = t.c_seg = 0;
+  return PS_OK;
+}
+static int task_segments(const ps_gemm_seg_desc& d, GTask& t) {
+  const int ms = d.m_seg == 0 ? d.m : d.m_seg;
+  if (ms < 1 || ms > d.m || d.m % ms != 0) return PS_EINVAL;
+  t.m_seg = ms;
+  t.seg_tm = (ms + TILE - 1) / TILE;
+  t.a_seg = t.c_seg = 0;
+  if (ms == d.m) return PS_OK;
+  if (!d.transa) return PS_EUNSUPPORTED;   // rows of a k-contiguous A are not segmented by any caller
+  t.a_seg = d.a_seg_stride;
+  t.c_seg = d.c_seg_stride;
+  return PS_OK;
+}
+
+template <class Desc>
+static int gplan_build(hipStream_t st, const Desc* desc, int count, void* workspace,
                        size_t workspace_bytes, ps_gemm_plan& pl) {
   if (!desc || count <= 0 || !workspace) return PS_EINVAL;
   const bool ah = pl.a_dtype == PS_DTYPE_BF16, bh = pl.b_dtype == PS_DTYPE_BF16;
+  if (bh && pl.seg) return PS_EUNSUPPORTED;   // no segmented instantiation reads a bf16 B
   if (ah || bh) {
     // the instantiations that exist: A bf16 with transa = 1, transb = 0; B bf16 with transa = transb = 0
     if (ah && bh) return PS_EUNSUPPORTED;
     for (int i = 0; i < count; ++i) {
-      const ps_gemm_desc& d = desc[i];
+      const Desc& d = desc[i];
       if ((ah && ((uintptr_t)d.a % 2 != 0)) || (bh && ((uintptr_t)d.b % 2 != 0))) return PS_EINVAL;
       if (d.transb || (ah && !d.transa) || (bh && d.transa)) return PS_EUNSUPPORTED;
     }
@@ -351,9 +441,9 @@ static int gplan_build(hipStream_t st, const ps_gemm_desc* desc, int count, void
   psh::Arena ar(workspace, workspace_bytes);
   const int total_tiles = (int)std::min<size_t>(grouped_total_tiles(desc, count), 1 << 30);
   for (int i = 0; i < count; ++i) {
-    const ps_gemm_desc& d = desc[i];
+    const Desc& d = desc[i];
     if (!d.a || !d.b || !d.c || d.m < 1 || d.n < 1 || d.k < 1 || d.ldc < d.n ||
-        d.lda < (d.transa ? d.m : d.k) || d.ldb < (d.transb ? d.k : d.n) ||
+        d.ldb < (d.transb ? d.k : d.n) ||
         d.lda > 0x7fffffff || d.ldb > 0x7fffffff || d.ldc > 0x7fffffff)
       return PS_EINVAL;
     const int g = (d.transa ? 2 : 0) + (d.transb ? 1 : 0);
@@ -361,6 +451,12 @@ static int gplan_build(hipStream_t st, const ps_gemm_desc* desc, int count, void
             (ah ? vec_ok_h(d.a, (int)d.lda) : vec_ok(d.a, (int)d.lda, 0)) ? 1 : 0,
             (bh ? vec_ok_h(d.b, (int)d.ldb) : vec_ok(d.b, (int)d.ldb, 0)) ? 1 : 0, 1, d.k,
             nullptr};
+    PS_RC(task_segments(d, t));
+    if (d.lda < (d.transa ? t.m_seg : d.k)) return PS_EINVAL;
+    // every segment starts as aligned as the first one (both storage types: a multiple of four elements)
+    if (t.a_seg % 4 != 0) t.veca = 0;
+    if (pl.seg && ((int64_t)(d.m / t.m_seg) * t.seg_tm > 0x7fff || (d.n + TILE - 1) / TILE > 0x7fff))
+      return PS_EUNSUPPORTED;   // GTile::tm / tn are 16-bit
     const int s = splitk_for(total_tiles, d.k);
     if (s > 1) {
       t.kchunk = psh::round_up((d.k + s - 1) / s, 128);   // keeps 16-byte load alignment
@@ -380,7 +476,7 @@ static int gplan_build(hipStream_t st, const ps_gemm_desc* desc, int count, void
     std::vector<int64_t> cost(tasks[g].size());
     for (size_t i = 0; i < tasks[g].size(); ++i) {
       const GTask& t = tasks[g][i];
-      const int tm = (t.m + TILE - 1) / TILE, tn = (t.n + TILE - 1) / TILE;
+      const int tm = (t.m / t.m_seg) * t.seg_tm, tn = (t.n + TILE - 1) / TILE;
       ntile[i] = tm * tn * t.ksplit;
       const bool gemv = (g == 0 || g == 2) && t.m == 1 && t.ksplit == 1;
       cost[i] = gemv ? 2 : (t.kchunk + 31) / 32 + 4;
@@ -414,10 +510,13 @@ static int gplan_build(hipStream_t st, const ps_gemm_desc* desc, int count, void
     PS_RC(psh::upload_async(st, pl.di[g], split_ids[g].data(), sizeof(int) * split_ids[g].size()));
   }
   static const bool lds_ok = [] {
-    const void* ks[6] = {(const void*)gemm_grouped_kernel<KC, MC>, (const void*)gemm_grouped_kernel<KC, KC>,
-                         (const void*)gemm_grouped_kernel<MC, MC>, (const void*)gemm_grouped_kernel<MC, KC>,
-                         (const void*)gemm_grouped_kernel<MC, MC, true, false>,
-                         (const void*)gemm_grouped_kernel<KC, MC, false, true>};
+    const void* ks[11] = {(const void*)gemm_grouped_kernel<KC, MC>, (const void*)gemm_grouped_kernel<KC, KC>,
+                          (const void*)gemm_grouped_kernel<MC, MC>, (const void*)gemm_grouped_kernel<MC, KC>,
+                          (const void*)gemm_grouped_kernel<MC, MC, true, false>,
+                          (const void*)gemm_grouped_kernel<KC, MC, false, true>,
+                          (const void*)gemm_grouped_seg_kernel<KC, MC>, (const void*)gemm_grouped_seg_kernel<KC, KC>,
+                          (const void*)gemm_grouped_seg_kernel<MC, MC>, (const void*)gemm_grouped_seg_kernel<MC, KC>,
+                          (const void*)gemm_grouped_seg_kernel<MC, MC, true>};
     for (const void* k : ks)
       (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 GEMM_GROUPED_LDS_BYTES);
@@ -439,10 +538,30 @@ static void gplan_launch_group(hipStream_t st, const ps_gemm_plan& pl, int G) {
                        pl.dt[G], pl.di[G]);
 }
 
+template <int LA, int LB, bool AH = false>
+static void gplan_launch_seg_group(hipStream_t st, const ps_gemm_plan& pl, int G) {
+  if (pl.ntiles[G] == 0) return;
+  const dim3 blk(256);
+  hipLaunchKernelGGL((gemm_grouped_seg_kernel<LA, LB, AH>), dim3((unsigned)pl.ntiles[G]), blk,
+                     GEMM_GROUPED_LDS_BYTES, st, pl.dt[G], pl.dl[G], pl.ntiles[G]);
+  if (pl.nsplit[G] > 0)
+    hipLaunchKernelGGL(gemm_splitk_reduce_seg_kernel, dim3((unsigned)pl.nsplit[G], 256), blk, 0, st,
+                       pl.dt[G], pl.di[G]);
+}
+
 static int gplan_launch(hipStream_t st, const ps_gemm_plan& pl) {
   // with a bf16 operand gplan_build admitted one layout group: 2 (transa = 1, A bf16) or
   // 0 (transa = transb = 0, B bf16)
-  if (pl.a_dtype == PS_DTYPE_BF16) {
+  if (pl.seg) {
+    if (pl.a_dtype == PS_DTYPE_BF16) {
+      gplan_launch_seg_group<MC, MC, true>(st, pl, 2);
+    } else {
+      gplan_launch_seg_group<KC, MC>(st, pl, 0);
+      gplan_launch_seg_group<KC, KC>(st, pl, 1);
+      gplan_launch_seg_group<MC, MC>(st, pl, 2);
+      gplan_launch_seg_group<MC, KC>(st, pl, 3);
+    }
+  } else if (pl.a_dtype == PS_DTYPE_BF16) {
     gplan_launch_group<MC, MC, true, false>(st, pl, 2);
   } else if (pl.b_dtype == PS_DTYPE_BF16) {
     gplan_launch_group<KC, MC, false, true>(st, pl, 0);
@@ -465,6 +584,21 @@ extern "C" int ps_gemm_grouped_typed(void* stream, const ps_gemm_desc* desc, int
   ps_gemm_plan pl;
   pl.a_dtype = a_dtype;
   pl.b_dtype = b_dtype;
+  PS_RC(gplan_build((hipStream_t)stream, desc, count, workspace, workspace_bytes, pl));
+  return gplan_launch((hipStream_t)stream, pl);
+}
+
+extern "C" int ps_gemm_grouped_seg_typed(void* stream, const ps_gemm_seg_desc* desc, int count,
+                                         int a_dtype, int b_dtype, void* workspace,
+                                         size_t workspace_bytes) {
+  if ((a_dtype != PS_DTYPE_F32 && a_dtype != PS_DTYPE_BF16) ||
+      (b_dtype != PS_DTYPE_F32 && b_dtype != PS_DTYPE_BF16))
+    return PS_EINVAL;
+  PS_DEVICE_CHECK();
+  ps_gemm_plan pl;
+  pl.a_dtype = a_dtype;
+  pl.b_dtype = b_dtype;
+  pl.seg = true;
   PS_RC(gplan_build((hipStream_t)stream, desc, count, workspace, workspace_bytes, pl));
   return gplan_launch((hipStream_t)stream, pl);
 }

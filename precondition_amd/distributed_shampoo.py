@@ -357,7 +357,7 @@ def distributed_shampoo(
   def _tree_plan(params_flat):
     """plan.TreePlan of this tree (shapes only), or None when the tree or the options need
     the general per-block path: FD / compression, owner-only statistics, blocks of merged
-    rank > 2, the host-logic test backend."""
+    rank > 3, partially preconditioned parameters, the host-logic test backend."""
     if (not hasattr(backend, "transform_grads_fused") or frequent_directions or
         compression_rank or shard_stats):
       return None
@@ -810,8 +810,11 @@ def distributed_shampoo(
     of parameters whose merged shape is 1-D or 2-D (the common case) are applied in
     two grouped launches — X_b = g_b^T P_L for every block, then Y_b = X_b^T P_R
     written straight into the merged gradient — instead of two products, a
-    transpose and a concatenation per block.  Everything else takes the per-block
-    path of blocking.Preconditioner."""
+    transpose and a concatenation per block.  With a tree plan, blocks of merged rank 3
+    (conv kernels, stacked expert weights) add their three contractions to those two
+    launches and a third one, reading the gradient block and writing the result in
+    place (plan.TreePlan.apply_preconditioners).  Everything else -- and every tree
+    without a plan -- takes the per-block path of blocking.Preconditioner below."""
     out = [None] * len(grads_flat)
     plan = _tree_plan(params_flat)
     if plan is not None and all(g.is_contiguous() for g in grads_flat):

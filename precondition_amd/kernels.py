@@ -415,6 +415,10 @@ def matmul(a: torch.Tensor, b: torch.Tensor, transa: bool = False,
 _GDESC_DT = np.dtype([("a", "u8"), ("b", "u8"), ("c", "u8"), ("m", "i4"), ("n", "i4"),
                       ("k", "i4"), ("transa", "i4"), ("transb", "i4"), ("lda", "i8"),
                       ("ldb", "i8"), ("ldc", "i8")], align=True)
+# ps_gemm_seg_desc: the same columns plus the split of the row index m (rows per segment, elements
+# between the segments of A and of C)
+_GSEGDESC_DT = np.dtype([(n, _GDESC_DT[n]) for n in _GDESC_DT.names] +
+                        [("m_seg", "i4"), ("a_seg_stride", "i8"), ("c_seg_stride", "i8")], align=True)
 
 
 def _ld_2d(shapes: np.ndarray, strides: np.ndarray) -> np.ndarray:

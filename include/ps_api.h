@@ -61,7 +61,7 @@
 extern "C" {
 #endif
 
-#define PS_VERSION 307 /* 0.3.7: PS_DTYPE_*, ps_*_typed (bf16 gradients / parameters / updates) */
+#define PS_VERSION 308 /* 0.3.8: ps_transform_grads_q8 (int8 momentum read and written where it lies) */
 
 enum {
   PS_OK = 0,
@@ -632,6 +632,59 @@ int ps_transform_grads_typed(void* stream, const ps_transform_desc* desc, int co
                              int grad_dtype,   /* grad AND upd_out */
                              int param_dtype,  /* param (read only with weight decay) */
                              void* workspace, size_t workspace_bytes);
+
+/* The same transform on int8 momentum (best_effort_memory_usage_reduction, DS:2047-2049, 3581-3586,
+ * 3617-3619): the momenta of a parameter are read as int8 codes + one float32 bucket size per column and
+ * written back as codes + bucket sizes; no float32 momentum exists outside registers.  Per parameter:
+ *   cols == 0  float32 momenta behind mom_* / dmom_* exactly as in ps_transform_desc (rank <= 1);
+ *   cols  > 0  both momenta are int8 codes viewed as [numel / cols, cols] (rows = shape[0], the view of
+ *              ps_quant_desc); the column of flat element i is i mod cols.  mom_* / dmom_* are ignored.
+ * Arithmetic per element, operation for operation the composition ps_dequantize_f32 ->
+ * ps_transform_grads_typed -> ps_quantize_f32:  mom = float(code) * bucket_in[col];  the transform;
+ * bucket_out[col] = max_r |new_mom[r, col]| / 127;  code = round_half_even(new_mom / (bucket_out[col] > 0 ?
+ * bucket_out[col] : 1)).  Update, diagonal statistics, codes and bucket sizes are that composition's bits.
+ * Launches: pass A, pass B (diagonal grafting), C1 (column maxima of the new momenta into the workspace),
+ * C2 (codes, update, diagonal statistics), one small launch for the bucket sizes; ordering comes from
+ * launch boundaries only.
+ * Aliasing: every x_out may alias x_in of the same parameter -- codes, bucket sizes, diag, float32
+ *   momenta.  diag_out, upd_out and the codes are stored only by the last pass over the elements, by the
+ *   thread that read the same element; bucket_out is written by the last launch, after every read of
+ *   bucket_in; column maxima accumulate in the workspace only.  Outputs must not alias anything of
+ *   ANOTHER parameter, nor an input of a different kind.
+ * Workspace: ps_transform_grads_q8_workspace_bytes (depends on numel and cols only).  Its contents on
+ *   entry do not matter; the maxima are zeroed inside the call.
+ * PS_EINVAL, with nothing written: cols < 0, numel % cols != 0, a NULL codes / bucket pointer with
+ *   cols > 0, a NULL float32 momentum pointer with cols == 0, odd bf16 pointers as in the typed entry.
+ *   numel == 0: no work, no pointer of the parameter is read. */
+typedef struct {
+  const float* grad;
+  const float* pgrad;
+  const float* param;
+  const float* diag_in;
+  float* diag_out;
+  const float* mom_in;    /* cols == 0 only */
+  float* mom_out;
+  const float* dmom_in;
+  float* dmom_out;
+  float* upd_out;
+  int64_t numel;
+  int64_t cols;
+  const int8_t* mom_codes_in;    /* [numel] int8, contiguous, any alignment */
+  int8_t* mom_codes_out;
+  const float* mom_bucket_in;    /* [cols] */
+  float* mom_bucket_out;
+  const int8_t* dmom_codes_in;
+  int8_t* dmom_codes_out;
+  const float* dmom_bucket_in;
+  float* dmom_bucket_out;
+} ps_transform_q8_desc;
+
+size_t ps_transform_grads_q8_workspace_bytes(const ps_transform_q8_desc* desc, int count);
+int ps_transform_grads_q8(void* stream, const ps_transform_q8_desc* desc, int count,
+                          const ps_transform_config* cfg,
+                          int grad_dtype,   /* grad AND upd_out */
+                          int param_dtype,  /* param (read only with weight decay) */
+                          void* workspace, size_t workspace_bytes);
 
 /* ---------------------------------------------------------------------------
  * Quantized optimizer state.  Replaces QuantizedValue.quantize

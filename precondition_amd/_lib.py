@@ -91,6 +91,14 @@ class TransformDesc(C.Structure):
                                          "upd_out")] + [("numel", C.c_int64)]
 
 
+class TransformQ8Desc(C.Structure):
+  """Mirror of ps_transform_q8_desc: ps_transform_desc plus the int8 momentum view."""
+  _fields_ = TransformDesc._fields_ + [("cols", C.c_int64)] + [
+      (n, C.c_void_p) for n in ("mom_codes_in", "mom_codes_out", "mom_bucket_in", "mom_bucket_out",
+                                "dmom_codes_in", "dmom_codes_out", "dmom_bucket_in",
+                                "dmom_bucket_out")]
+
+
 class TransformConfig(C.Structure):
   """Mirror of ps_transform_config."""
   _fields_ = [(n, C.c_int32) for n in ("graft_type", "nesterov",
@@ -292,6 +300,10 @@ _SIGNATURES = {
                    C.c_void_p, C.c_size_t]),
     "ps_transform_grads_typed":
         (C.c_int, [C.c_void_p, C.POINTER(TransformDesc), C.c_int, C.POINTER(TransformConfig),
+                   C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
+    "ps_transform_grads_q8_workspace_bytes": (C.c_size_t, [C.POINTER(TransformQ8Desc), C.c_int]),
+    "ps_transform_grads_q8":
+        (C.c_int, [C.c_void_p, C.POINTER(TransformQ8Desc), C.c_int, C.POINTER(TransformConfig),
                    C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
     "ps_comm_unique_id": (C.c_int, [C.c_void_p]),
     "ps_comm_init": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p]),

@@ -22,6 +22,7 @@
 
 #include "common.h"
 #include "options.h"
+#include "quant_math.h"   // encode1: the division and rounding of QU:91-94
 
 namespace psk {
 
@@ -157,7 +158,6 @@ __global__ __launch_bounds__(256) void quant_colmax_kernel(const QTensor* ts, co
 constexpr int QFLAT = 16384;      // elements per chunk (16 float4 per thread)
 constexpr int QFLAT_MAXC = 8192;  // columns kept in LDS by the column-max pass
 constexpr int QMAXT = 1 << 30;
-__device__ inline int encode1(float x, float bs_nonzero);
 
 // FULL: the chunk lies inside the tensor (every chunk but a tensor's last): no per-lane bounds tests.
 // With them every load sits behind a divergent branch and the compiler waits for it before the next one:
@@ -312,10 +312,6 @@ __global__ __launch_bounds__(256) void quant_flat_kernel(const QTensor* ts, cons
       if (a) atomicMax(t->colmax + c, a);
     }
   }
-}
-
-__device__ inline int encode1(float x, float bs_nonzero) {
-  return (int)rintf(__fdiv_rn(x, bs_nonzero));  // QU:91-94; rint = round half to even
 }
 
 // ---- quantize in ONE read (round 6): register-resident column strips -----------------------------------------

@@ -167,9 +167,14 @@ def distributed_shampoo(
     # returned state holds the same tensors, and the returned updates live in buffers the optimizer
     # owns (valid until the next update call) -- no allocation, no descriptor rebuilt, the same
     # seven launches (plan.DonatedStep).  The state passed in must not be used afterwards.  Applies
-    # to dense states (the tree-plan path; the state itself is float32) with gradients that are
-    # uniformly float32 or uniformly bfloat16 -- the latter are read where they lie and the updates
-    # come back in bfloat16; anything else takes the functional path.
+    # to dense states (the tree-plan path) with gradients that are uniformly float32 or uniformly
+    # bfloat16 -- the latter are read where they lie and the updates come back in bfloat16.  The
+    # state is float32, or -- best_effort_memory_usage_reduction without a batch axis -- float32
+    # with int8 momentum: codes and bucket sizes are updated where they lie
+    # (ps_transform_grads_q8), the returned QuantizedValues are the ones passed in.  Anything
+    # else takes the functional path exactly as before: int16 statistics and preconditioners
+    # (best_effort_memory_usage_reduction with a batch axis), lobpcg_topk_precondition, and every
+    # recompute step.
     donate_state: bool = False,
     _backend_for_testing: Any = None,
 ):
@@ -986,7 +991,7 @@ def distributed_shampoo(
     """update() on a donated state (steps without a root recompute): the updates, or None when
     this step / state takes the functional path."""
     if (_backend_for_testing is not None or quantize_second_moment or
-        best_effort_memory_usage_reduction or lobpcg_topk_precondition or _recompute_step(step)):
+        lobpcg_topk_precondition or _recompute_step(step)):
       return None
     plan = _tree_plan(params_flat)
     if plan is None or not stats_flat:
@@ -999,9 +1004,9 @@ def distributed_shampoo(
     gdt = grads_flat[0].dtype
     if not ds.bound_to(stats_flat) or ds.gdtype != gdt:   # (a change of gradient dtype binds again)
       ok = (all(isinstance(st, ParameterStats) and
-                st.momentum.quantized_dtype == torch.float32 and
-                st.diagonal_momentum.quantized_dtype == torch.float32 and
-                isinstance(st.avg_grad, MaskedNode) for st in stats_flat) and
+                st.momentum.quantized_dtype == quantized_dtype_for_momentum_buffers(p) and
+                st.diagonal_momentum.quantized_dtype == st.momentum.quantized_dtype and
+                isinstance(st.avg_grad, MaskedNode) for st, p in zip(stats_flat, params_flat)) and
             all(g.dtype == gdt and g.is_contiguous() for g in grads_flat))
       if not ok or not ds.bind(stats_flat, grads_flat, params_flat, symmetric_precs=True):
         return None
@@ -1024,7 +1029,8 @@ def distributed_shampoo(
           grad=g, pgrad=None if skipped else pg,
           param=p if weight_decay != 0 else None,
           diag_in=s.diagonal_statistics.to_float() if has_diag else None,
-          mom_in=s.momentum.to_float(), dmom_in=s.diagonal_momentum.to_float()))
+          mom_in=_momentum_operand(s.momentum),
+          dmom_in=_momentum_operand(s.diagonal_momentum)))
     cfg = dict(
         graft_type=int(graft_type), nesterov=int(bool(nesterov)),
         moving_average_for_momentum=int(bool(moving_average_for_momentum)),
@@ -1041,9 +1047,19 @@ def distributed_shampoo(
     for (upd, nd, mom, dmom), s in zip(res, states):
       new_diag = nd if has_diag else s.diagonal_statistics.to_float()
       outs.append((upd, ParameterStats(_quantize(new_diag), s.statistics, s.preconditioners,
-                                       _quantize(dmom), _quantize(mom), s.avg_grad,
+                                       _momentum_result(dmom), _momentum_result(mom), s.avg_grad,
                                        s.training_metrics)))
     return outs
+
+  def _momentum_operand(m):
+    """Int8 momentum goes to the kernel as it lies (codes + bucket sizes); the rest as float32."""
+    return m if m.quantized_dtype == torch.int8 else m.to_float()
+
+  def _momentum_result(m):
+    """(codes, bucket_size) of an int8 momentum, or the float32 tensor."""
+    if isinstance(m, tuple):
+      return QuantizedValue(m[0], [], m[1], torch.int8, False, list(m[0].shape))
+    return _quantize(m)
 
   def _at_the_door(grads_flat, params_flat, native_bf16):
     """Gradients and parameters as the kernels read them: float32 copies, or -- native_bf16 -- the
@@ -1087,14 +1103,15 @@ def distributed_shampoo(
     new_stats = _compute_stats_all(grads_flat, stats_flat, params_flat, step)
     new_stats = _compute_preconditioners(new_stats, params_flat, step)
     pgs = _preconditioned_grads_all(grads_flat, new_stats, params_flat)
-    if best_effort_memory_usage_reduction:
+    fused = hasattr(backend, "transform_grads_fused")   # reads and writes int8 momentum where it lies
+    if best_effort_memory_usage_reduction and not fused:
       # int8 momentum (DS:3581-3586 to_float): dequantize the whole tree in one launch
       n = len(new_stats)
       fl = _to_float_many([s.momentum for s in new_stats] +
                           [s.diagonal_momentum for s in new_stats])
       new_stats = [s._replace(momentum=_quantize(fl[i]), diagonal_momentum=_quantize(fl[n + i]))
                    for i, s in enumerate(new_stats)]
-    if hasattr(backend, "transform_grads_fused"):
+    if fused:
       outs = _transform_grads_fused(grads_flat, new_stats, params_flat, pgs, step)
     else:  # host-logic test seam: the same arithmetic as torch elementwise ops
       outs = [_transform_grad(g, s, p, step, pg)
@@ -1102,7 +1119,7 @@ def distributed_shampoo(
     updates_flat = [o[0] if o[0].dtype == dt else o[0].to(dt)
                     for o, dt in zip(outs, grad_dtypes)]
     new_stats = [o[1] for o in outs]
-    if best_effort_memory_usage_reduction:  # _quantize_momentum, DS:3617-3619
+    if best_effort_memory_usage_reduction and not fused:  # _quantize_momentum, DS:3617-3619
       moms = _quantize_momentum_many([s.momentum.to_float() for s in new_stats], params_flat)
       dmoms = _quantize_momentum_many([s.diagonal_momentum.to_float() for s in new_stats],
                                       params_flat)
@@ -1269,21 +1286,22 @@ def distributed_shampoo(
     # CAME IN with (the roots computed below reach the update of the NEXT step), unlike the
     # pmap path, which roots first (DS:3648-3650).  Pinned by tests/golden/e2e_sharded.npz.
     pgs = _preconditioned_grads_all(grads_flat, new_stats, params_flat)
-    if best_effort_memory_usage_reduction:
+    fused = hasattr(backend, "transform_grads_fused")   # reads and writes int8 momentum where it lies
+    if best_effort_memory_usage_reduction and not fused:
       # int8 momentum (DS:3581-3586 to_float): dequantize the whole tree in one launch
       n_p = len(new_stats)
       fl = _to_float_many([s_.momentum for s_ in new_stats] +
                           [s_.diagonal_momentum for s_ in new_stats])
       new_stats = [s_._replace(momentum=_quantize(fl[i]), diagonal_momentum=_quantize(fl[n_p + i]))
                    for i, s_ in enumerate(new_stats)]
-    if hasattr(backend, "transform_grads_fused"):
+    if fused:
       outs = _transform_grads_fused(grads_flat, new_stats, params_flat, pgs, step)
     else:
       outs = [_transform_grad(g, s, p, step, pg)
               for g, s, p, pg in zip(grads_flat, new_stats, params_flat, pgs)]
     updates_flat = [o[0] if o[0].dtype == dt else o[0].to(dt) for o, dt in zip(outs, grad_dtypes)]
     stats_flat = [o[1] for o in outs]
-    if best_effort_memory_usage_reduction:
+    if best_effort_memory_usage_reduction and not fused:
       mq = _quantize_momentum_many(
           [s_.momentum.to_float() for s_ in stats_flat] +
           [s_.diagonal_momentum.to_float() for s_ in stats_flat], params_flat + params_flat)

@@ -15,7 +15,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import GemmDesc, StatsDesc, TransformConfig, TransformDesc, check, lib
+from ._lib import (GemmDesc, StatsDesc, TransformConfig, TransformDesc, TransformQ8Desc, check,
+                   lib)
 
 
 def _require_gpu(t: torch.Tensor, what: str):
@@ -1110,6 +1111,17 @@ def fd_update_root_batched(calls):
 _TDESC_DT = np.dtype([(n, "u8") for n in ("grad", "pgrad", "param", "diag_in", "diag_out",
                                           "mom_in", "mom_out", "dmom_in", "dmom_out",
                                           "upd_out")] + [("numel", "i8")], align=True)
+# ps_transform_q8_desc: the same columns, then the int8 view of both momenta
+_TQDESC_DT = np.dtype([(n, _TDESC_DT[n]) for n in _TDESC_DT.names] + [("cols", "i8")] +
+                      [(n, "u8") for n in ("mom_codes_in", "mom_codes_out", "mom_bucket_in",
+                                           "mom_bucket_out", "dmom_codes_in", "dmom_codes_out",
+                                           "dmom_bucket_in", "dmom_bucket_out")], align=True)
+
+
+def _is_q8(m) -> bool:
+  """A QuantizedValue holding int8 codes (duck-typed: state.py imports this module)."""
+  q = getattr(m, "quantized", None)
+  return q is not None and q.dtype == torch.int8
 
 
 # Capability flag read by distributed_shampoo.update_fn: this backend's every-step calls (the tree
@@ -1127,13 +1139,26 @@ def transform_grads_fused(items, cfg: dict):
   (update, new_diag|None, new_mom, new_dmom).  cfg: fields of ps_transform_config.
   `grad` (and with it the update) is float32 or bfloat16, one dtype for the whole list; so is
   `param`, independently; everything else is float32 in and out.
+  An item whose mom_in AND dmom_in are QuantizedValues with int8 codes (best_effort_memory_usage_
+  reduction) is read where it lies: the whole list goes through ps_transform_grads_q8, and such an item
+  gets (update, new_diag|None, (codes, bucket_size), (codes, bucket_size)) back -- no float32 momentum
+  is made for it.
   The descriptor table is filled column-wise with NumPy."""
   if not items:
     return []
   n = len(items)
   dev = items[0]["grad"].device
-  assert _TDESC_DT.itemsize == C.sizeof(TransformDesc)
-  tbl = np.zeros(n, _TDESC_DT)
+  quant = [_is_q8(it["mom_in"]) for it in items]
+  q8 = any(quant)
+  if q8:
+    for i, it in enumerate(items):
+      if _is_q8(it["dmom_in"]) != quant[i]:
+        raise ValueError(f"_transform_grad: item {i} has one int8 and one float32 momentum")
+    qitems = items
+    items = [dict(it, mom_in=None, dmom_in=None) if q else it for it, q in zip(items, quant)]
+  desc_dt, desc_t = (_TQDESC_DT, TransformQ8Desc) if q8 else (_TDESC_DT, TransformDesc)
+  assert desc_dt.itemsize == C.sizeof(desc_t)
+  tbl = np.zeros(n, desc_dt)
   keep = []
 
   def column(name, required=False, typed=False):
@@ -1169,23 +1194,48 @@ def transform_grads_fused(items, cfg: dict):
   upd = [torch.empty_like(g) for g in grads]      # the gradient's dtype
   # state is float32 whatever the gradient's dtype (empty_like(g) would follow a bfloat16 gradient)
   f32_like = lambda g: torch.empty(g.shape, dtype=torch.float32, device=g.device)
-  mom = [f32_like(g) for g in grads]
-  dmom = [f32_like(g) for g in grads]
+  mom = [None if q else f32_like(g) for g, q in zip(grads, quant)]
+  dmom = [None if q else f32_like(g) for g, q in zip(grads, quant)]
   nd = [f32_like(g) if h else None for g, h in zip(grads, has_diag)]
   tbl["upd_out"] = [t.data_ptr() for t in upd]
-  tbl["mom_out"] = [t.data_ptr() for t in mom]
-  tbl["dmom_out"] = [t.data_ptr() for t in dmom]
+  tbl["mom_out"] = [0 if t is None else t.data_ptr() for t in mom]
+  tbl["dmom_out"] = [0 if t is None else t.data_ptr() for t in dmom]
   tbl["diag_out"] = [0 if t is None else t.data_ptr() for t in nd]
   tbl["numel"] = [g.numel() for g in grads]
+  if q8:
+    for i, (it, g) in enumerate(zip(qitems, grads)):
+      if not quant[i]:
+        continue
+      tbl["cols"][i] = _as_rows_cols(g.shape)[1]
+      for name, key in (("mom", "mom_in"), ("dmom", "dmom_in")):
+        qv = it[key]
+        codes, bucket = qv.quantized, qv.bucket_size
+        if (not codes.is_cuda or codes.numel() != g.numel() or bucket.dtype != torch.float32 or
+            (g.numel() and bucket.numel() != tbl["cols"][i])):
+          _require_gpu(codes, "_transform_grad")
+          raise ValueError(f"_transform_grad: int8 {key} of item {i} does not match its gradient")
+        codes = codes if codes.is_contiguous() else codes.contiguous()
+        bucket = bucket if bucket.is_contiguous() else bucket.contiguous()
+        out = (torch.empty_like(codes), torch.empty_like(bucket))
+        keep.append((codes, bucket))
+        tbl[name + "_codes_in"][i], tbl[name + "_bucket_in"][i] = codes.data_ptr(), bucket.data_ptr()
+        tbl[name + "_codes_out"][i], tbl[name + "_bucket_out"][i] = out[0].data_ptr(), out[1].data_ptr()
+        (mom if name == "mom" else dmom)[i] = out
   c = TransformConfig()
   for k, v in cfg.items():
     setattr(c, k, v)
-  descs = C.cast(tbl.ctypes.data, C.POINTER(TransformDesc))
+  descs = C.cast(tbl.ctypes.data, C.POINTER(desc_t))
   L = lib()
-  ws = _workspace(L.ps_transform_grads_workspace_bytes(descs, n), dev)
-  rc = L.ps_transform_grads_typed(_stream(), descs, n, C.byref(c), grad_code, param_code,
-                                  ws.data_ptr(), ws.numel())
-  check(rc, "ps_transform_grads_typed")
+  if q8:
+    ws = _workspace(L.ps_transform_grads_q8_workspace_bytes(descs, n), dev)
+    rc = L.ps_transform_grads_q8(_stream(), descs, n, C.byref(c), grad_code, param_code,
+                                 ws.data_ptr(), ws.numel())
+    check(rc, "ps_transform_grads_q8")
+  else:
+    ws = _workspace(L.ps_transform_grads_workspace_bytes(descs, n), dev)
+    rc = L.ps_transform_grads_typed(_stream(), descs, n, C.byref(c), grad_code, param_code,
+                                    ws.data_ptr(), ws.numel())
+    check(rc, "ps_transform_grads_typed")
   del keep
   return list(zip(upd, nd, mom, dmom))
 

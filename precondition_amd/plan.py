@@ -432,7 +432,8 @@ class DonatedStep:
   the counterpart of the reference's jit-compiled update_fn (DS:3627-3659), which does no per-step
   host work beyond the dispatch.
 
-  The state tensors (statistics, diagonal statistics, both momenta) are updated IN PLACE, the
+  The state tensors (statistics, diagonal statistics, both momenta -- float32, or int8 codes and their
+  bucket sizes through ps_transform_grads_q8) are updated IN PLACE, the
   preconditioned gradients, the intermediates of the application (X of the two-sided products,
   X1 / X2 of the rank-3 blocks) and the updates live in buffers this object owns, so every pointer
   column of the descriptor tables (Gram update, application stages A, B and -- rank-3 blocks -- C,
@@ -468,7 +469,22 @@ class DonatedStep:
     diags = [st.diagonal_statistics.quantized for st in stats_flat] if self.has_diag else []
     if len(stats) != len(pl.stat_dims) or len(precs) != len(pl.stat_dims):
       return False
-    pl.check_dense(stats + precs + moms + dmoms + diags, "update (donated state)")
+    # int8 momenta (best_effort_memory_usage_reduction): codes + bucket sizes, updated where they lie
+    quant = [m.dtype == torch.int8 for m in moms]
+    if any((d.dtype == torch.int8) != q for d, q in zip(dmoms, quant)):
+      return False
+    qidx = [i for i, q in enumerate(quant) if q]
+    mbuckets = [stats_flat[i].momentum.bucket_size for i in qidx]
+    dbuckets = [stats_flat[i].diagonal_momentum.bucket_size for i in qidx]
+    for i, mb, db in zip(qidx, mbuckets, dbuckets):
+      cols = kernels._as_rows_cols(moms[i].shape)[1]
+      if (not moms[i].is_cuda or not moms[i].is_contiguous() or not dmoms[i].is_contiguous() or
+          moms[i].numel() != pl.numel[i] or dmoms[i].numel() != pl.numel[i] or
+          (pl.numel[i] and (mb.numel() != cols or db.numel() != cols))):
+        return False
+    pl.check_dense(stats + precs + [m for m, q in zip(moms, quant) if not q] +
+                   [m for m, q in zip(dmoms, quant) if not q] + mbuckets + dbuckets + diags,
+                   "update (donated state)")
     n = pl.n_params
     self.dev = dev
     # buffers owned by the step (valid until the next update call)
@@ -515,9 +531,21 @@ class DonatedStep:
     self.ta = _with_rank3(self.ta, r1)
     self.tb = _with_rank3(tb, r2)
     # ---- _transform_grad, in place ----
-    tt = np.zeros(n, kernels._TDESC_DT)
+    self.q8 = bool(qidx)
+    self.tdesc = kernels.TransformQ8Desc if self.q8 else kernels.TransformDesc
+    tt = np.zeros(n, kernels._TQDESC_DT if self.q8 else kernels._TDESC_DT)
     tt["pgrad"] = rp
     mp, dp = pl._ptrs(moms), pl._ptrs(dmoms)
+    if self.q8:
+      isq = np.array(quant)
+      zero = np.uint64(0)
+      tt["cols"] = [kernels._as_rows_cols(m.shape)[1] if q else 0 for m, q in zip(moms, quant)]
+      for name, codes, buckets in (("mom", mp, mbuckets), ("dmom", dp, dbuckets)):
+        bp = np.zeros(n, np.uint64)
+        bp[qidx] = pl._ptrs(buckets)
+        tt[name + "_codes_in"] = tt[name + "_codes_out"] = np.where(isq, codes, zero)
+        tt[name + "_bucket_in"] = tt[name + "_bucket_out"] = bp
+      mp, dp = np.where(isq, zero, mp), np.where(isq, zero, dp)
     tt["mom_in"] = mp; tt["mom_out"] = mp
     tt["dmom_in"] = dp; tt["dmom_out"] = dp
     if self.has_diag:
@@ -536,8 +564,8 @@ class DonatedStep:
                                          for t in (self.ta, self.tb, self.tc))
       tt_probe = self.tt.copy()
       tt_probe["grad"] = tt_probe["upd_out"]   # sizes only
-      self.ws_t = ws_for(L.ps_transform_grads_workspace_bytes(
-          C.cast(tt_probe.ctypes.data, C.POINTER(kernels.TransformDesc)), n))
+      ws_bytes = L.ps_transform_grads_q8_workspace_bytes if self.q8 else L.ps_transform_grads_workspace_bytes
+      self.ws_t = ws_for(ws_bytes(C.cast(tt_probe.ctypes.data, C.POINTER(self.tdesc)), n))
     self.objs = list(stats_flat)
     self.gp = None
     self.pp_params = None
@@ -607,8 +635,9 @@ class DonatedStep:
       c = kernels.TransformConfig()
       for k, v in cfg.items():
         setattr(c, k, v)
-      rc = L.ps_transform_grads_typed(stream, C.cast(self.tt.ctypes.data, C.POINTER(kernels.TransformDesc)),
-                                      self.plan.n_params, C.byref(c), gcode, pcode,
-                                      self.ws_t.data_ptr(), self.ws_t.numel())
-      check(rc, "ps_transform_grads_typed")
+      transform = L.ps_transform_grads_q8 if self.q8 else L.ps_transform_grads_typed
+      rc = transform(stream, C.cast(self.tt.ctypes.data, C.POINTER(self.tdesc)),
+                     self.plan.n_params, C.byref(c), gcode, pcode,
+                     self.ws_t.data_ptr(), self.ws_t.numel())
+      check(rc, "ps_transform_grads_q8" if self.q8 else "ps_transform_grads_typed")
     return self.upd

@@ -22,6 +22,8 @@ if "--quant" in sys.argv:  # int8 momentum + int16 statistics / preconditioners 
   dist.init_process_group("nccl", store=dist.FileStore(os.path.join(tempfile.mkdtemp(), "s"), 1),
                           rank=0, world_size=1)
   kw = dict(best_effort_memory_usage_reduction=True, batch_axis_name=dist.group.WORLD)
+if "--quant-momentum" in sys.argv:  # int8 momentum only (no process group): the mode the donated path takes
+  kw = dict(best_effort_memory_usage_reduction=True)
 if "--donate" in sys.argv:   # the in-place, allocation-free every-step path (plan.DonatedStep)
   kw["donate_state"] = True
 opt = pa.distributed_shampoo(0.1, 1024, preconditioning_compute_steps=50, start_preconditioning_step=1, graft_type=pa.GraftingType.RMSPROP_NORMALIZED, **kw)
@@ -57,6 +59,20 @@ for t in range(3):
 torch.cuda.synchronize(); pr.disable()
 pstats.Stats(pr).sort_stats("cumulative").print_stats(18)
 pstats.Stats(pr).sort_stats("tottime").print_stats(22)
+# device-event time of the every-step work (events around 8 steps, none of them a recompute), and what a step adds at its peak to the memory held before it
+e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+torch.cuda.synchronize(); e0.record()
+for t in range(8):
+  upd, st = opt.update(grads, st, params)
+e1.record(); torch.cuda.synchronize()
+print(f"device-event time: {e0.elapsed_time(e1) / 8:.3f} ms/step (GPU time where the host keeps the queue full)")
+del upd
+torch.cuda.synchronize(); torch.cuda.reset_peak_memory_stats()
+m0 = torch.cuda.memory_allocated()
+upd, st = opt.update(grads, st, params)
+torch.cuda.synchronize()
+print(f"step peak over the memory held before it: {(torch.cuda.max_memory_allocated() - m0) / 2**20:.1f} MiB "
+      f"(after the step: {(torch.cuda.memory_allocated() - m0) / 2**20:+.1f} MiB)")
 nbytes = sum(x.numel() * x.element_size() for x in pa.pytree.tree_leaves(st) if isinstance(x, torch.Tensor))
 print(f"optimizer state: {nbytes / 2**20:.1f} MiB")
 if "--quant" in sys.argv:

@@ -410,7 +410,17 @@ int ps_eigh_root_batched_opt_f32(void* stream, const float* const* a, const int3
  * back in LAPACK's ASCENDING order; larger ones in the Jacobi order (NOT sorted): callers
  * that need ascending order sort those pairs.  Used by the low-rank /
  * Frequent-Directions branch (_low_rank_root DS:1033-1120, _fd_update_root DS:1123-1290).
- * Workspace: ps_eigh_root_workspace_bytes. */
+ * Workspace: ps_eigh_root_workspace_bytes.
+ * Input range and indefinite inputs, n <= 128 (tests/test_gpu_eigh_solvers.py): the kernel works on
+ * A 2^-k with max|a_ij| 2^-k in [1, 2) and scales the eigenvalues back, so any finite float32 matrix is
+ * solved to the accuracy of a matrix of unit size (measured on Wishart and GOE matrices x 2^34 and x 2^-50;
+ * entries within a factor 4 of FLT_MAX may overflow in the symmetrisation (a + a^T) / 2).  Indefinite
+ * matrices, including those whose eigenvalues +x and -x coincide in magnitude (symmetric orthogonal
+ * matrices, bipartite forms [[0, B], [B^T, 0]]), are detected and solved once more as A + shift I: eigenvalues
+ * within max(4 x ssyevd's error, 2e-6 ||A||), residual and orthogonality within 2e-5.  A matrix with a NaN
+ * or infinite entry returns NaN for EVERY eigenvalue (its eigenvector array holds the identity) and does not
+ * affect the other matrices of the batch.  n > 128: the two-sided solver (PS_EIGH_TWO_SIDED) meets 3e-6 /
+ * 3e-6 / 5e-6 or 4 x ssyevd's error on the same inputs, the scaled ones included. */
 int ps_eigh_sorted_max_n(void);
 int ps_eigh_batched_f32(void* stream, const float* const* a, const int32_t* n,
                         const int32_t* lda, int batch, float* const* evals,

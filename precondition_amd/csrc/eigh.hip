@@ -461,16 +461,51 @@ __global__ __launch_bounds__(SE_T) void eigh_small_kernel(EighBlock* blocks, con
   const int lane = tid & 63, wave = tid >> 6;
   float shift = 0.f;
   int sweeps_total = 0;
+  // The sweeps run on A 2^-sexp, max|a_ij| scaled into [1, 2): the squared column norms and their
+  // products stay inside the float32 range whatever the magnitude of the input (unscaled, aa * bb
+  // overflows from entries of ~4e8 on and underflows below ~1e-10: no pair rotates / every pair
+  // rotates on noise).  A power of two commutes with every operation below, so an input that needed
+  // no scaling gives the same bits; the eigenvalues are scaled back where they are written.  A
+  // non-finite entry makes every eigenvalue NaN (finite = false: G is NaN, nothing rotates).
+  int* s_amax = s_rot + 2;
+  int* s_mixed = s_rot + 3;
+  if (tid == 0) { *s_amax = 0; *s_mixed = 0; }
+  __syncthreads();
+  int sexp = 0;
+  bool finite = true;
   // One-sided Jacobi yields the SVD: for an indefinite matrix with eigenvalues +x and -x of
   // close magnitude the singular subspace mixes their eigenvectors.  Such inputs (detected
   // from the Rayleigh quotients) are solved again as A + shift I, which is positive definite.
   for (int attempt = 0; attempt < 2; ++attempt) {
-    // G = (D + D^T)/2 + shift I column-major, zero padded to 128 rows / m columns; V = I
+    // G = ((D + D^T)/2) 2^-sexp + shift I column-major, zero padded to 128 rows / m columns; V = I
+    if (attempt == 0) {
+      // max|a_ij| as the bit pattern of a non-negative float: integer order is float order there,
+      // +inf sorts above every finite value and NaN above +inf
+      int amax = 0;
+      for (int e = tid; e < SE_MAXN * SE_MAXN; e += SE_T) {
+        const int col = e >> 7, row = e & 127;
+        float g = 0.f;
+        if (row < n && col < n)
+          g = 0.5f * (gload1(A + (int64_t)col * ld + row) + gload1(A + (int64_t)row * ld + col));
+        G[col * SE_LD + row] = g;
+        amax = max(amax, __float_as_int(fabsf(g)));
+      }
+      amax = (int)wave_max_u32((unsigned)amax);
+      if (lane == 0) atomicMax(s_amax, amax);
+      __syncthreads();
+      amax = *s_amax;
+      finite = amax < 0x7f800000;
+      // max|a_ij| 2^-sexp lies in [1, 2) (a subnormal maximum: below 1)
+      sexp = amax == 0 ? 0 : ((amax >> 23) & 0xff) - 127;
+    }
     for (int e = tid; e < SE_MAXN * SE_MAXN; e += SE_T) {
       const int col = e >> 7, row = e & 127;
       float g = 0.f;
       if (row < n && col < n) {
-        g = 0.5f * (gload1(A + (int64_t)col * ld + row) + gload1(A + (int64_t)row * ld + col));
+        // each thread reads back the elements it staged itself
+        g = attempt == 0 ? G[col * SE_LD + row]
+                         : 0.5f * (gload1(A + (int64_t)col * ld + row) + gload1(A + (int64_t)row * ld + col));
+        g = finite ? ldexpf(g, -sexp) : nanf("");
         if (row == col) g += shift;
       }
       G[col * SE_LD + row] = g;
@@ -514,10 +549,10 @@ __global__ __launch_bounds__(SE_T) void eigh_small_kernel(EighBlock* blocks, con
         const int col = e >> 7, row = e & 127;
         float g = 0.f;
         if (row < n && col < n) {
-          g = 0.5f * (gload1(A + (int64_t)col * ld + row) + gload1(A + (int64_t)row * ld + col));
+          g = ldexpf(0.5f * (gload1(A + (int64_t)col * ld + row) + gload1(A + (int64_t)row * ld + col)), -sexp);
           if (row == col) g += shift;
         }
-        G[col * SE_LD + row] = g;    // the (symmetric) matrix itself, column-major
+        G[col * SE_LD + row] = g;    // the (symmetric, scaled) matrix itself, column-major
       }
       __syncthreads();
       double ng[SE_MAXN * SE_MAXN / SE_T];
@@ -544,6 +579,8 @@ __global__ __launch_bounds__(SE_T) void eigh_small_kernel(EighBlock* blocks, con
     // The approximate rcp / rsq of the rotation parameters scale a rotation by 1 + O(eps):
     // renormalise the eigenvectors (and g_j with them, G = A V), then the Rayleigh quotients.
     float lo_ev = 0.f, hi_abs = 0.f;
+    float* s_gn = s_red + 32;     // [128] ||g_j||: the area holds s_ev / s_rank once the sweeps are over
+    float* s_vg = s_gn + 128;     // [128] |v_j . g_j|
     for (int j = wave; j < m; j += SE_T / 64) {
       const float v0 = V[j * SE_LD + lane], v1 = V[j * SE_LD + 64 + lane];
       const float nn = wave_sum_f32(v0 * v0 + v1 * v1);
@@ -551,11 +588,15 @@ __global__ __launch_bounds__(SE_T) void eigh_small_kernel(EighBlock* blocks, con
       const float g0 = G[j * SE_LD + lane] * inv, g1 = G[j * SE_LD + 64 + lane] * inv;
       V[j * SE_LD + lane] = v0 * inv; V[j * SE_LD + 64 + lane] = v1 * inv;
       G[j * SE_LD + lane] = g0; G[j * SE_LD + 64 + lane] = g1;
-      const float ev = wave_sum_f32(v0 * inv * g0 + v1 * inv * g1) - shift;
+      const float vg = wave_sum_f32(v0 * inv * g0 + v1 * inv * g1);
+      const float ev = vg - shift;
       // ||g_j|| = the singular value |lambda_j + shift|: exact even when eigenvectors of +x and
       // -x are mixed, so 1.01 max_j ||g_j|| is a safe shift
       const float gn = sqrtf(wave_sum_f32(g0 * g0 + g1 * g1));
-      if (j < n) { lo_ev = fminf(lo_ev, ev); hi_abs = fmaxf(hi_abs, gn); }
+      if (j < n) {
+        lo_ev = fminf(lo_ev, ev); hi_abs = fmaxf(hi_abs, gn);
+        if (lane == 0) { s_gn[j] = gn; s_vg[j] = fabsf(vg); }
+      }
     }
     if (lane == 0) { s_red[wave] = lo_ev; }
     __syncthreads();
@@ -569,7 +610,16 @@ __global__ __launch_bounds__(SE_T) void eigh_small_kernel(EighBlock* blocks, con
     __syncthreads();
     // positive semi-definite (the statistics, Gram and Rayleigh-Ritz matrices of this
     // library): done.  Clearly indefinite: once more on A + 1.01 max|lambda| I.
-    if (attempt == 1 || !(lo_all < -1e-5f * hi_all)) break;
+    if (attempt == 1) break;
+    // Mixing that leaves no negative quotient behind (symmetric orthogonal matrices: no pair ever
+    // rotates, lambda = diag(A); bipartite forms [[0, B], [B^T, 0]]: every quotient is exactly 0):
+    // an eigenvector has |v_j . g_j| = ||g_j|| up to rounding, while a -x eigenvector spread over
+    // m <= 128 columns of a degenerate singular subspace leaves one of them with at least 1/m of
+    // it, |v_j . g_j| <= (1 - 2/128) ||g_j||.  Columns below 1e-5 max ||g|| (the null space of a
+    // semi-definite input, carried as rounding noise) are not judged.
+    if (tid < n && s_gn[tid] > 1e-5f * hi_all && s_vg[tid] < (1.f - 1e-2f) * s_gn[tid]) *s_mixed = 1;
+    __syncthreads();
+    if (!(lo_all < -1e-5f * hi_all) && !*s_mixed) break;
     shift = 1.01f * hi_all;
   }
   if (eb->evals_out != nullptr) {
@@ -582,7 +632,7 @@ __global__ __launch_bounds__(SE_T) void eigh_small_kernel(EighBlock* blocks, con
       float d = V[j * SE_LD + lane] * G[j * SE_LD + lane] +
                 V[j * SE_LD + 64 + lane] * G[j * SE_LD + 64 + lane];
       d = wave_sum_f32(d);
-      if (lane == 0) s_ev[j] = d - shift;
+      if (lane == 0) s_ev[j] = ldexpf(d - shift, sexp);
     }
     __syncthreads();
     if (tid < n) {
@@ -620,7 +670,7 @@ __global__ __launch_bounds__(SE_T) void eigh_small_kernel(EighBlock* blocks, con
     float d = V[j * SE_LD + lane] * G[j * SE_LD + lane] +
               V[j * SE_LD + 64 + lane] * G[j * SE_LD + 64 + lane];
     d = wave_sum_f32(d);
-    if (lane == 0) gstore1(Aout + (int64_t)j * ld + j, d - shift);
+    if (lane == 0) gstore1(Aout + (int64_t)j * ld + j, ldexpf(d - shift, sexp));
   }
   if (tid == 0) { eb->sweeps = sweeps_total; eb->active = 0; eb->off_rel = 0.f; }
 }

@@ -288,7 +288,14 @@ def eigh_batched(matrices: Sequence[torch.Tensor], options=None):
   eigenvectors [n, n] in columns) per matrix, LAPACK order; signs of eigenvectors are arbitrary.
   `options`: eigh_solver / eigh_sweep_tol / eigh_streams of _lib.make_options (default 'auto':
   the tridiagonalisation path where the matrix is positive definite and well conditioned, the
-  Jacobi solvers -- accurate relative to every eigenvalue -- otherwise)."""
+  Jacobi solvers -- accurate relative to every eigenvalue -- otherwise).
+
+  Any finite float32 input is in range: matrices of up to 128 rows are scaled by a power of two inside the
+  kernel (max|a_ij| near 1) and the eigenvalues scaled back; above that the tridiagonal and the two-sided
+  solver are tested on inputs scaled by 2^34 / 2^-50 and 1e18 / 1e-20.  Indefinite inputs are supported, +x / -x eigenvalue pairs of equal magnitude
+  included (exchange matrices, Householder reflectors, adjacency matrices of bipartite graphs): the small
+  kernel detects them and re-solves A + shift I.  A matrix with a NaN or infinite entry gets NaN for every
+  eigenvalue; its batch mates are unaffected (tests/test_gpu_eigh_solvers.py)."""
   batch = len(matrices)
   dev = matrices[0].device
   for m in matrices:

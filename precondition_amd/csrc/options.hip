@@ -46,8 +46,6 @@ void ps_dev_env_overrides(Options& o) {
   geti("PS_EIGH_TD_STAGE", o.eigh_td_stage);
   geti("PS_EIGH_TD_STREAMS", o.eigh_td_streams);
   geti("PS_EIGH_TD_TAIL", o.eigh_td_tail);
-  geti("PS_QUANT_FLAT", o.quant_flat);
-  geti("PS_QUANT_STRIP", o.quant_strip);
   geti("PS_FD_GROUPS", o.fd_groups);
 }
 

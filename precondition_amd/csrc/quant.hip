@@ -5,51 +5,27 @@
 //   bucket[c]  = max_r |x[r, c]| / B          B = 127 (int8) or 32767 (int16)                  QU:85-86
 //   code[r, c] = round_half_even(x[r, c] / (bucket[c] > 0 ? bucket[c] : 1))                    QU:89-94
 //   to_float   = float(code) * bucket[c]  (+ diagonal on the diagonal)                         QU:108-112
-// All of it is elementwise IEEE float32 arithmetic, so codes, diagonals and bucket sizes are
-// BIT-EXACT with the reference; the only reduction is a max, which is order independent.
+// All of it is elementwise IEEE float32 arithmetic (quant_math.h), so codes, diagonals and bucket sizes are
+// BIT-EXACT with the reference on every path; the only reduction is a max, taken on the bit patterns (exact for
+// non-negative floats; a NaN has the largest bit pattern and therefore propagates like jnp.max).
 //
-// HBM-bound byte work.  A tensor is viewed as [rows, cols] (rows = shape[0], the axis the
-// reference reduces over) and cut into chunks of 64 rows x 256 columns; one 256-thread
-// workgroup per chunk, for every tensor of the tree in ONE launch per pass:
-//   pass 1  column max of |x| per chunk (float4 per lane: a wavefront reads 1 KiB of a row),
-//           combined across chunks with atomicMax on the float bits (exact for non-negative
-//           floats; a NaN has the largest bit pattern and therefore propagates like jnp.max);
-//   pass 2  re-reads the chunk (L2 / Infinity-Cache resident for typical statistics), divides,
-//           rounds to nearest even and stores 8 B (int16) or 4 B (int8) per lane.
-// Algorithmic bytes per element: 4 (read) + 2 or 1 (write) for quantize (the second read is the
-// price of the column-max dependency), 2 or 1 + 4 for dequantize.
-#include <vector>
-
+// HBM-bound byte work.  A tensor is viewed as [rows, cols] (rows = shape[0], the axis the reference reduces over).
+// The host plan (quant_plan.h: which tensor takes which path, and why) puts every tensor of a descriptor list on
+// ONE path and every path's work items into one list: a call is at most five launches for any number of tensors.
+//   quantize    strip + small  quant_strip_kernel: ONE read, codes from registers (4 + 2 or 1 bytes per element);
+//                              small tensors of any layout at the head of the same grid (quant_small_body)
+//               flat           quant_flat_kernel<0>, <1>: column maxima, then codes, over chunks of consecutive
+//                              elements (the second read is the price of the column-max dependency)
+//               tile           quant_colmax_kernel, quant_encode_kernel: the same two passes over 64 x 256 tiles, a
+//                              float4 branch (`vec4`) and a one-column-per-lane branch, 64-bit indices throughout
+//   dequantize  flat + tile    quant_decode_all_kernel: one launch, the tile chunks at the head of the grid
 #include "common.h"
-#include "options.h"
-#include "quant_math.h"   // encode1: the division and rounding of QU:91-94
+#include "quant_math.h"   // the arithmetic of QU:85-94 and QU:109, four codes <-> one store
+#include "quant_plan.h"   // QTensor, QuantPlan: who takes which path
 
 namespace psk {
 
 #define PS_GLOBAL __attribute__((address_space(1)))
-
-constexpr int QW = 256;  // columns per chunk
-constexpr int QR = 64;   // rows per chunk
-
-struct QTensor {
-  const float* fin;   // quantize input
-  float* fout;        // dequantize output
-  void* codes;
-  float* diag;
-  float* bucket;
-  unsigned* colmax;   // workspace: bit patterns of the column maxima (quantize only)
-  long long rows, cols, ld, ldq;
-  int bits, extract, vec4;
-  int chunk0, strips;
-  int flat;               // contiguous [rows, cols] float4-addressable tensor: the flat kernels take it
-  int fchunk0, fchunks;   // its chunks of QFLAT consecutive elements
-  int strip;              // quantize only: the register-resident strip kernel takes it (quant_strip_kernel)
-  int schunk0, schunks;   // its strips of QS_COLS columns
-  int small;              // quantize only: workgroups at the head of the strip launch take it (quant_small_body):
-  int small_w;            //   every one ALL rows of a range of small_w columns
-  int team;               // strips of more than 1024 rows: parts of 1024 rows, one workgroup each (1 = whole strips)
-  unsigned* sarrive;      // workspace: per strip, the parts whose column maxima are merged
-};
 
 typedef float qf4 __attribute__((ext_vector_type(4)));
 struct F4 { float x, y, z, w; };
@@ -74,46 +50,53 @@ __device__ inline unsigned ldg1u_so(const void* ubase, uint32_t lane_off) {
   return *(const unsigned PS_GLOBAL*)((const char PS_GLOBAL*)ubase + (uint64_t)lane_off);
 }
 
-// ---- pass 1: column maxima -------------------------------------------------------------
-__global__ __launch_bounds__(256) void quant_colmax_kernel(const QTensor* ts, const int* cmap, int chunk_base) {
-  __shared__ unsigned red[4][QW];
-  const int chunk = blockIdx.x + chunk_base;
+// ---- tile kernels: chunks of QR rows x QW columns ---------------------------------------
+// chunk -> tensor (per-chunk table: one 4-byte load), column strip, rows [r0, r1)
+struct QTile { const QTensor* t; int strip, rc; long long r0, r1; };
+__device__ __forceinline__ QTile quant_tile(const QTensor* ts, const int* cmap, int chunk) {
   const QTensor* t = &ts[cmap[chunk]];
-  if (t->flat) return;   // quant_flat_kernel took it
   const int local = chunk - t->chunk0;
   const int strip = local % t->strips, rc = local / t->strips;
-  const int tid = threadIdx.x;
-  const long long rows = t->rows, cols = t->cols, ld = t->ld;
   const long long r0 = (long long)rc * QR;
-  const long long r1 = r0 + QR < rows ? r0 + QR : rows;
+  return {t, strip, rc, r0, r0 + QR < t->rows ? r0 + QR : t->rows};
+}
+
+// float4 branch: rows r0 + wave + 4 u of the lane's four columns, ALL 16 in flight (independent 16-byte loads)
+// before the first use: with four the kernels ran at 3.7 TB/s (latency-bound), the same access shape streams at
+// 6 TB/s (tools/bench_symv.hip v1).  Rows from r1 on are zeros.
+__device__ __forceinline__ void quant_tile_load16(const QTensor* t, int strip, long long r0, long long r1, int wave,
+                                                  int lane, F4 (&v)[16]) {
+  const long long ld = t->ld;
+  uint32_t loff = (uint32_t)((wave * ld + lane * 4) * 4);
+  asm volatile("" : "+v"(loff));
+  const float* ub = t->fin + r0 * ld + (long long)strip * QW;   // wave-uniform
+#pragma unroll
+  for (int u = 0; u < 16; ++u)
+    v[u] = r0 + wave + 4 * u < r1 ? ldg4_so(ub + (long long)(4 * u) * ld, loff) : F4{0.f, 0.f, 0.f, 0.f};
+}
+
+// pass 1: column maxima
+__global__ __launch_bounds__(256) void quant_colmax_kernel(const QTensor* ts, const int* cmap) {
+  __shared__ unsigned red[4][QW];
+  const auto [t, strip, rc, r0, r1] = quant_tile(ts, cmap, (int)blockIdx.x);
+  const int tid = threadIdx.x;
+  const long long cols = t->cols, ld = t->ld;
   if (t->vec4) {
     const int wave = tid >> 6, lane = tid & 63;
     const long long col = (long long)strip * QW + lane * 4;
     unsigned m[4] = {0u, 0u, 0u, 0u};
     if (col < cols) {
-      // all 16 rows of the lane in flight (independent 16-byte loads) before the first use: with four
-      // the kernel ran at 3.7 TB/s (latency-bound), the same access shape streams at 6 TB/s
-      // (tools/bench_symv.hip v1)
-      uint32_t loff = (uint32_t)((wave * ld + lane * 4) * 4);
-      asm volatile("" : "+v"(loff));
-      for (long long rb = r0 + wave; rb == r0 + wave; rb += 64) {   // QR = 64 rows: one pass
-        F4 v[16];
-        const float* ub = t->fin + (rb - wave) * ld + (long long)strip * QW;   // wave-uniform
+      F4 v[16];
+      quant_tile_load16(t, strip, r0, r1, wave, lane, v);
 #pragma unroll
-        for (int u = 0; u < 16; ++u) {
-          const long long r = rb + 4 * u;
-          v[u] = r < r1 ? ldg4_so(ub + (long long)(4 * u) * ld, loff) : F4{0.f, 0.f, 0.f, 0.f};
-        }
+      for (int u = 0; u < 16; ++u) {
+        const long long r = r0 + wave + 4 * u;
+        float x[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
 #pragma unroll
-        for (int u = 0; u < 16; ++u) {
-          const long long r = rb + 4 * u;
-          float x[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            if (t->extract && col + j == r) x[j] = __fsub_rn(x[j], x[j]);   // QU:79-80 (NaN for a non-finite diagonal)
-            const unsigned b = __float_as_uint(fabsf(x[j]));
-            m[j] = b > m[j] ? b : m[j];
-          }
+        for (int j = 0; j < 4; ++j) {
+          if (t->extract && col + j == r) x[j] = __fsub_rn(x[j], x[j]);   // QU:79-80 (NaN for a non-finite diagonal)
+          const unsigned b = __float_as_uint(fabsf(x[j]));
+          m[j] = b > m[j] ? b : m[j];
         }
       }
     }
@@ -149,16 +132,12 @@ __global__ __launch_bounds__(256) void quant_colmax_kernel(const QTensor* ts, co
   }
 }
 
-// ---- flat kernels (round 5): chunks of 16384 CONSECUTIVE elements ---------------------------------------
+// ---- flat kernels: chunks of QFLAT = 16384 CONSECUTIVE elements -----------------------------------------
 // A contiguous [rows, cols] tensor is streamed in runs of 64 KB (whole rows, back to back) instead of
 // 64-row x 1 KB tiles: the 1 KB row pieces of a tile land in different DRAM pages (measured: the tile
 // form decodes at 2.5 TB/s).  Column of an element = its flat offset mod cols, tracked incrementally;
 // the column maxima of a chunk are merged in LDS (ds_max_u32) and flushed with one global atomicMax
 // per column.  Same arithmetic as the tile kernels, bit for bit.
-constexpr int QFLAT = 16384;      // elements per chunk (16 float4 per thread)
-constexpr int QFLAT_MAXC = 8192;  // columns kept in LDS by the column-max pass
-constexpr int QMAXT = 1 << 30;
-
 // FULL: the chunk lies inside the tensor (every chunk but a tensor's last): no per-lane bounds tests.
 // With them every load sits behind a divergent branch and the compiler waits for it before the next one:
 // the sixteen loads of a lane are then issued one after the other (measured: half the rate of the same
@@ -169,7 +148,7 @@ __device__ __forceinline__ void quant_flat_chunk(const QTensor* t, int local, un
   const long long cols = t->cols, rows = t->rows, total = rows * cols;
   const long long base = (long long)local * QFLAT;
   const int extract = t->extract;
-  const float nb = BITS == 8 ? 127.f : 32767.f;
+  const float nb = num_buckets(BITS);
   // incremental (row, col) of the thread's float4s: offsets base + 4 tid + 1024 k
   const long long off0 = base + 4 * tid;
   int row = (int)(off0 / cols);                      // rows * cols <= QMAXT: 32-bit row / column arithmetic
@@ -214,7 +193,7 @@ __device__ __forceinline__ void quant_flat_chunk(const QTensor* t, int local, un
     }
   }
   if (MODE == 1 && local == 0) {   // bucket sizes (QU:86), once per tensor
-    for (int c = tid; c < cols; c += 256) t->bucket[c] = __fdiv_rn(__uint_as_float(t->colmax[c]), nb);
+    for (int c = tid; c < cols; c += 256) t->bucket[c] = bucket_size(t->colmax[c], nb);
   }
 #pragma unroll
   for (int k = 0; k < 16; ++k) {
@@ -236,8 +215,7 @@ __device__ __forceinline__ void quant_flat_chunk(const QTensor* t, int local, un
         int q[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const float bs = __fdiv_rn(__uint_as_float(cmv[j]), nb);   // QU:86
-          const float bnz = bs > 0.f ? bs : 1.f;                       // QU:89-90
+          const float bnz = bucket_nonzero(bucket_size(cmv[j], nb));
           if (extract && col + j == row) {
             *(float PS_GLOBAL*)(t->diag + row) = x[j];
             x[j] = __fsub_rn(x[j], x[j]);
@@ -247,30 +225,20 @@ __device__ __forceinline__ void quant_flat_chunk(const QTensor* t, int local, un
         const long long o = off0 + 1024 * k;
         if (BITS == 16) {
           typedef unsigned u2v __attribute__((ext_vector_type(2)));
-          u2v pk;
-          pk[0] = ((unsigned)q[0] & 0xffffu) | ((unsigned)q[1] << 16);
-          pk[1] = ((unsigned)q[2] & 0xffffu) | ((unsigned)q[3] << 16);
-          *(u2v PS_GLOBAL*)(reinterpret_cast<short*>(t->codes) + o) = pk;
+          const uint2 pk = pack4_i16(q);
+          *(u2v PS_GLOBAL*)(reinterpret_cast<short*>(t->codes) + o) = u2v{pk.x, pk.y};
         } else {
-          const unsigned pk = ((unsigned)q[0] & 0xffu) | (((unsigned)q[1] & 0xffu) << 8) |
-                              (((unsigned)q[2] & 0xffu) << 16) | ((unsigned)q[3] << 24);
-          *(unsigned PS_GLOBAL*)(reinterpret_cast<signed char*>(t->codes) + o) = pk;
+          *(unsigned PS_GLOBAL*)(reinterpret_cast<signed char*>(t->codes) + o) = pack4_i8(q);
         }
       } else {
         int q[4];
-        if (BITS == 16) {
-          q[0] = (short)(pk16[k].x & 0xffffu); q[1] = (short)(pk16[k].x >> 16);
-          q[2] = (short)(pk16[k].y & 0xffffu); q[3] = (short)(pk16[k].y >> 16);
-        } else {
-          const unsigned pk = pk8[k];
-          q[0] = (signed char)(pk & 0xffu); q[1] = (signed char)((pk >> 8) & 0xffu);
-          q[2] = (signed char)((pk >> 16) & 0xffu); q[3] = (signed char)(pk >> 24);
-        }
+        if (BITS == 16) unpack4_i16(pk16[k], q);
+        else unpack4_i8(pk8[k], q);
         const F4 b4 = ldg4(t->bucket + col);
         const float bs[4] = {b4.x, b4.y, b4.z, b4.w};
         qf4 x;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) x[j] = __fmul_rn((float)q[j], bs[j]);          // QU:109
+        for (int j = 0; j < 4; ++j) x[j] = decode1(q[j], bs[j]);
         const int dj = row - col;
         if (extract && (unsigned)dj < 4u) {                                         // QU:111
 #pragma unroll
@@ -284,20 +252,10 @@ __device__ __forceinline__ void quant_flat_chunk(const QTensor* t, int local, un
   }
 }
 
-template <int MODE>   // 0 = column maxima, 1 = encode, 2 = decode
-__global__ __launch_bounds__(256) void quant_flat_kernel(const QTensor* ts, const int* cmap) {
-  __shared__ unsigned s_max[MODE == 0 ? QFLAT_MAXC : 1];
-  // chunk -> tensor from a per-chunk table (one 4-byte load)
-  const QTensor* t = &ts[cmap[blockIdx.x]];
-  const int local = blockIdx.x - t->fchunk0;
-  const int tid = threadIdx.x;
-  const long long cols = t->cols;
-  if (MODE == 0) {
-    for (int c = tid; c < cols; c += 256) s_max[c] = 0u;
-    __syncthreads();
-  }
+// one chunk of tensor t: inside the tensor or its last one, int16 or int8 codes (MODE 0 does not depend on the width)
+template <int MODE>
+__device__ __forceinline__ void quant_flat_dispatch(const QTensor* t, int local, long long cols, unsigned* s_max) {
   const bool full = (long long)(local + 1) * QFLAT <= t->rows * cols;
-  // (MODE 0 does not depend on the code width)
   if (MODE == 0 || t->bits == 16) {
     if (full) quant_flat_chunk<MODE, true, 16>(t, local, s_max);
     else quant_flat_chunk<MODE, false, 16>(t, local, s_max);
@@ -305,6 +263,21 @@ __global__ __launch_bounds__(256) void quant_flat_kernel(const QTensor* ts, cons
     if (full) quant_flat_chunk<MODE, true, 8>(t, local, s_max);
     else quant_flat_chunk<MODE, false, 8>(t, local, s_max);
   }
+}
+
+template <int MODE>   // 0 = column maxima, 1 = encode, 2 = decode
+__global__ __launch_bounds__(256) void quant_flat_kernel(const QTensor* ts, const int* cmap) {
+  __shared__ unsigned s_max[MODE == 0 ? QFLAT_MAXC : 1];
+  // chunk -> tensor from a per-chunk table (one 4-byte load)
+  const QTensor* t = &ts[cmap[blockIdx.x]];
+  const int local = blockIdx.x - t->chunk0;
+  const int tid = threadIdx.x;
+  const long long cols = t->cols;
+  if (MODE == 0) {
+    for (int c = tid; c < cols; c += 256) s_max[c] = 0u;
+    __syncthreads();
+  }
+  quant_flat_dispatch<MODE>(t, local, cols, s_max);
   if (MODE == 0) {
     __syncthreads();
     for (int c = tid; c < cols; c += 256) {
@@ -323,11 +296,6 @@ __global__ __launch_bounds__(256) void quant_flat_kernel(const QTensor* ts, cons
 // instruction and has all of a lane's loads in flight at once (<= 32 x 16 bytes per lane, 256 KB per workgroup); int16
 // codes leave as whole 128-byte lines.  Same arithmetic as the other kernels (IEEE division, round half to even, the
 // maximum taken on bit patterns): codes, diagonals and bucket sizes are bit-identical.
-constexpr int QS_COLS = 64;
-constexpr int QS_THREADS = 512;
-constexpr int QS_GROUPS = QS_THREADS / 16;   // 32 row groups
-constexpr int QS_NV = 32;                    // rows per lane: up to 32 x 32 = 1024 rows
-constexpr int QS_MINR = 64;                  // below that a strip is too little work per workgroup
 
 // Instruction count matters as much as bytes here: a workgroup's 65536 elements pass through the VALU twice (maximum,
 // codes) behind loads that cannot overlap them (one workgroup per CU).  The first version spent ~45 instructions per
@@ -378,7 +346,7 @@ __device__ __forceinline__ P* qs_uni(P* p) {
 __device__ __forceinline__ QsStrip qs_strip(const QTensor* ts, const int* cmap, int idx, int wave) {
   const QTensor* t = &ts[qs_uni(cmap[idx])];
   QsStrip s;
-  const int local = idx - qs_uni(t->schunk0);
+  const int local = idx - qs_uni(t->chunk0);
   s.team = qs_uni(t->team);
   const int strip = local / s.team, part = local - strip * s.team;
   const int rows_all = qs_uni((int)t->rows);                        // rows_all * cols * 4 < 2^31
@@ -400,9 +368,6 @@ __device__ __forceinline__ QsStrip qs_strip(const QTensor* ts, const int* cmap, 
 // the strip launch, one workgroup each, FIRST in the grid: column maxima through LDS, then the codes from a second
 // read (L2).  As launches of their own (tile kernels: two passes, two launches) they ran 20-50 us behind the big kernel
 // on the same stream.  Same arithmetic as every other path: bit-identical codes.
-constexpr int QSM_ELEMS = 65536;
-constexpr int QSM_COLS = 2048;
-
 // item = (tensor, first column): ALL rows of a range of up to `width` columns (QTensor::small_w; rows * width <=
 // QSM_ELEMS, width <= QSM_COLS).  Columns are independent, so a wide and short tensor ([1, 197, 768] embeddings:
 // 151 296 columns of one row) is simply many items.
@@ -416,7 +381,7 @@ __device__ __forceinline__ void quant_small_body(const QTensor* t, int c0, unsig
   float* const diag = t->diag;
   float* const bucket = t->bucket;
   const int extract = t->extract, bits = t->bits;
-  const float nb = bits == 8 ? 127.f : 32767.f;
+  const float nb = num_buckets(bits);
   for (int c = tid; c < nc; c += QS_THREADS) s_max[c] = 0u;
   __syncthreads();
   // pass 1: a lane keeps the running maximum of the column it is in and merges it when the column changes
@@ -449,9 +414,9 @@ __device__ __forceinline__ void quant_small_body(const QTensor* t, int c0, unsig
   }
   __syncthreads();
   for (int c = tid; c < nc; c += QS_THREADS) {
-    const float bs = __fdiv_rn(__uint_as_float(s_max[c]), nb);   // QU:86
+    const float bs = bucket_size(s_max[c], nb);
     bucket[c0 + c] = bs;
-    s_max[c] = __float_as_uint(bs > 0.f ? bs : 1.f);             // QU:89-90
+    s_max[c] = __float_as_uint(bucket_nonzero(bs));
   }
   __syncthreads();
   for (int e0 = tid; e0 < total; e0 += 8 * QS_THREADS) {
@@ -517,7 +482,7 @@ __global__ __launch_bounds__(QS_THREADS) void quant_strip_kernel(const QTensor* 
     const int rows = cur.rows, cols = cur.cols;
     const int col = cur.c0 + 4 * q;
     const bool col_in = col < cols;
-    const float nb = cur.bits == 8 ? 127.f : 32767.f;
+    const float nb = num_buckets(cur.bits);
     const int nv_used = (rows + QS_GROUPS - 1) / QS_GROUPS;
     // diagonal: row 32 k + g meets the strip's columns [c0, c0 + 64) only for k = c0 / 32 and k = c0 / 32 + 1
     if (cur.extract) {
@@ -616,8 +581,8 @@ __global__ __launch_bounds__(QS_THREADS) void quant_strip_kernel(const QTensor* 
     const bool writes_bucket = g == 0 && col_in && cur.r_off == 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float bs = __fdiv_rn(__uint_as_float(amax[j]), nb);   // QU:86
-      bnz[j] = bs > 0.f ? bs : 1.f;                          // QU:89-90
+      const float bs = bucket_size(amax[j], nb);
+      bnz[j] = bucket_nonzero(bs);
       if (writes_bucket) *(float PS_GLOBAL*)(cur.bucket + col + j) = bs;
       // the denominator-only part of the IEEE division sequence
       const float rc = __builtin_amdgcn_rcpf(bnz[j]);
@@ -687,18 +652,12 @@ __global__ __launch_bounds__(QS_THREADS) void quant_strip_kernel(const QTensor* 
   }
 }
 
-// ---- pass 2: bucket sizes, diagonal, codes ---------------------------------------------
-__global__ __launch_bounds__(256) void quant_encode_kernel(const QTensor* ts, const int* cmap, int chunk_base) {
-  const int chunk = blockIdx.x + chunk_base;
-  const QTensor* t = &ts[cmap[chunk]];
-  if (t->flat) return;   // quant_flat_kernel took it
-  const int local = chunk - t->chunk0;
-  const int strip = local % t->strips, rc = local / t->strips;
+// ---- tile pass 2: bucket sizes, diagonal, codes -----------------------------------------
+__global__ __launch_bounds__(256) void quant_encode_kernel(const QTensor* ts, const int* cmap) {
+  const auto [t, strip, rc, r0, r1] = quant_tile(ts, cmap, (int)blockIdx.x);
   const int tid = threadIdx.x;
-  const long long rows = t->rows, cols = t->cols, ld = t->ld, ldq = t->ldq;
-  const long long r0 = (long long)rc * QR;
-  const long long r1 = r0 + QR < rows ? r0 + QR : rows;
-  const float nb = t->bits == 8 ? 127.f : 32767.f;
+  const long long cols = t->cols, ld = t->ld, ldq = t->ldq;
+  const float nb = num_buckets(t->bits);
   if (t->vec4) {
     const int wave = tid >> 6, lane = tid & 63;
     const long long col = (long long)strip * QW + lane * 4;
@@ -706,49 +665,34 @@ __global__ __launch_bounds__(256) void quant_encode_kernel(const QTensor* ts, co
     float bs[4], bnz[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      bs[j] = __fdiv_rn(__uint_as_float(t->colmax[col + j]), nb);  // QU:86
-      bnz[j] = bs[j] > 0.f ? bs[j] : 1.f;                          // QU:89-90
+      bs[j] = bucket_size(t->colmax[col + j], nb);
+      bnz[j] = bucket_nonzero(bs[j]);
     }
     if (rc == 0 && wave == 0)
       *reinterpret_cast<float4*>(t->bucket + col) = make_float4(bs[0], bs[1], bs[2], bs[3]);
-    uint32_t loff = (uint32_t)((wave * ld + lane * 4) * 4);
-    asm volatile("" : "+v"(loff));
-    for (long long rb = r0 + wave; rb == r0 + wave; rb += 64) {   // QR = 64 rows: one pass
-      F4 v[16];
-      const float* ub = t->fin + (rb - wave) * ld + (long long)strip * QW;   // wave-uniform
+    F4 v[16];
+    quant_tile_load16(t, strip, r0, r1, wave, lane, v);
 #pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        const long long r = rb + 4 * u;
-        v[u] = r < r1 ? ldg4_so(ub + (long long)(4 * u) * ld, loff) : F4{0.f, 0.f, 0.f, 0.f};
+    for (int u = 0; u < 16; ++u) {
+      const long long r = r0 + wave + 4 * u;
+      if (r >= r1) continue;   // (not `break`: the loop must unroll completely, or v[] lives in scratch)
+      float x[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+      int q[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (t->extract && col + j == r) { t->diag[r] = x[j]; x[j] = __fsub_rn(x[j], x[j]); }
+        q[j] = encode1(x[j], bnz[j]);
       }
-#pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        const long long r = rb + 4 * u;
-        if (r >= r1) continue;   // (not `break`: the loop must unroll completely, or v[] lives in scratch)
-        float x[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-        int q[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if (t->extract && col + j == r) { t->diag[r] = x[j]; x[j] = __fsub_rn(x[j], x[j]); }
-          q[j] = encode1(x[j], bnz[j]);
-        }
-        if (t->bits == 16) {
-          uint2 pk;
-          pk.x = ((unsigned)q[0] & 0xffffu) | ((unsigned)q[1] << 16);
-          pk.y = ((unsigned)q[2] & 0xffffu) | ((unsigned)q[3] << 16);
-          *reinterpret_cast<uint2*>(reinterpret_cast<short*>(t->codes) + r * ldq + col) = pk;
-        } else {
-          const unsigned pk = ((unsigned)q[0] & 0xffu) | (((unsigned)q[1] & 0xffu) << 8) |
-                              (((unsigned)q[2] & 0xffu) << 16) | ((unsigned)q[3] << 24);
-          *reinterpret_cast<unsigned*>(reinterpret_cast<signed char*>(t->codes) + r * ldq + col) = pk;
-        }
-      }
+      if (t->bits == 16)
+        *reinterpret_cast<uint2*>(reinterpret_cast<short*>(t->codes) + r * ldq + col) = pack4_i16(q);
+      else
+        *reinterpret_cast<unsigned*>(reinterpret_cast<signed char*>(t->codes) + r * ldq + col) = pack4_i8(q);
     }
   } else {
     const long long c = (long long)strip * QW + tid;
     if (c >= cols) return;
-    const float bs = __fdiv_rn(__uint_as_float(t->colmax[c]), nb);
-    const float bnz = bs > 0.f ? bs : 1.f;
+    const float bs = bucket_size(t->colmax[c], nb);
+    const float bnz = bucket_nonzero(bs);
     const float* const fin = t->fin;
     float* const diag = t->diag;
     void* const codes = t->codes;
@@ -773,14 +717,9 @@ __global__ __launch_bounds__(256) void quant_encode_kernel(const QTensor* ts, co
 
 // ---- to_float --------------------------------------------------------------------------
 __device__ __forceinline__ void quant_decode_tile(const QTensor* ts, const int* cmap, int chunk) {
-  const QTensor* t = &ts[cmap[chunk]];
-  if (t->flat) return;
-  const int local = chunk - t->chunk0;
-  const int strip = local % t->strips, rc = local / t->strips;
+  const auto [t, strip, rc, r0, r1] = quant_tile(ts, cmap, chunk);
   const int tid = threadIdx.x;
-  const long long rows = t->rows, cols = t->cols, ld = t->ld, ldq = t->ldq;
-  const long long r0 = (long long)rc * QR;
-  const long long r1 = r0 + QR < rows ? r0 + QR : rows;
+  const long long cols = t->cols, ld = t->ld, ldq = t->ldq;
   if (t->vec4) {
     const int wave = tid >> 6, lane = tid & 63;
     const long long col = (long long)strip * QW + lane * 4;
@@ -792,40 +731,33 @@ __device__ __forceinline__ void quant_decode_tile(const QTensor* ts, const int* 
     const int esz = t->bits == 16 ? 2 : 1;
     uint32_t loff = (uint32_t)((wave * ldq + lane * 4) * esz);
     asm volatile("" : "+v"(loff));
-    for (long long rb = r0 + wave; rb == r0 + wave; rb += 64) {   // QR = 64 rows: one pass
-      uint2 pk16[16];
-      unsigned pk8[16];
-      const char* ub = reinterpret_cast<const char*>(t->codes) + ((rb - wave) * ldq + (long long)strip * QW) * esz;
+    const long long rb = r0 + wave;   // QR = 64 rows: one pass
+    uint2 pk16[16];
+    unsigned pk8[16];
+    const char* ub = reinterpret_cast<const char*>(t->codes) + (r0 * ldq + (long long)strip * QW) * esz;
 #pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        const long long r = rb + 4 * u;
-        pk16[u] = uint2{0u, 0u}; pk8[u] = 0u;
-        if (r < r1) {
-          if (t->bits == 16) pk16[u] = ldg2u_so(ub + (long long)(4 * u) * ldq * 2, loff);
-          else pk8[u] = ldg1u_so(ub + (long long)(4 * u) * ldq, loff);
-        }
+    for (int u = 0; u < 16; ++u) {
+      const long long r = rb + 4 * u;
+      pk16[u] = uint2{0u, 0u}; pk8[u] = 0u;
+      if (r < r1) {
+        if (t->bits == 16) pk16[u] = ldg2u_so(ub + (long long)(4 * u) * ldq * 2, loff);
+        else pk8[u] = ldg1u_so(ub + (long long)(4 * u) * ldq, loff);
       }
+    }
 #pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        const long long r = rb + 4 * u;
-        if (r >= r1) continue;   // (not `break`: the loop must unroll completely, or v[] lives in scratch)
-        int q[4];
-        if (t->bits == 16) {
-          q[0] = (short)(pk16[u].x & 0xffffu); q[1] = (short)(pk16[u].x >> 16);
-          q[2] = (short)(pk16[u].y & 0xffffu); q[3] = (short)(pk16[u].y >> 16);
-        } else {
-          const unsigned pk = pk8[u];
-          q[0] = (signed char)(pk & 0xffu); q[1] = (signed char)((pk >> 8) & 0xffu);
-          q[2] = (signed char)((pk >> 16) & 0xffu); q[3] = (signed char)(pk >> 24);
-        }
-        float x[4];
+    for (int u = 0; u < 16; ++u) {
+      const long long r = rb + 4 * u;
+      if (r >= r1) continue;   // (not `break`: the loop must unroll completely, or v[] lives in scratch)
+      int q[4];
+      if (t->bits == 16) unpack4_i16(pk16[u], q);
+      else unpack4_i8(pk8[u], q);
+      float x[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          x[j] = __fmul_rn((float)q[j], bs[j]);                                     // QU:109
-          if (t->extract && col + j == r) x[j] = __fadd_rn(x[j], t->diag[r]);       // QU:111
-        }
-        *reinterpret_cast<float4*>(t->fout + r * ld + col) = make_float4(x[0], x[1], x[2], x[3]);
+      for (int j = 0; j < 4; ++j) {
+        x[j] = decode1(q[j], bs[j]);
+        if (t->extract && col + j == r) x[j] = __fadd_rn(x[j], t->diag[r]);       // QU:111
       }
+      *reinterpret_cast<float4*>(t->fout + r * ld + col) = make_float4(x[0], x[1], x[2], x[3]);
     }
   } else {
     const long long c = (long long)strip * QW + tid;
@@ -848,7 +780,7 @@ __device__ __forceinline__ void quant_decode_tile(const QTensor* ts, const int* 
       for (int u = 0; u < 8; ++u) {
         const long long r = rb + u;
         if (r >= r1) break;
-        float x = __fmul_rn((float)q[u], bs);                   // QU:109
+        float x = decode1(q[u], bs);
         if (extract && c == r) x = __fadd_rn(x, dg);            // QU:111
         fout[r * ld + c] = x;
       }
@@ -859,161 +791,52 @@ __device__ __forceinline__ void quant_decode_tile(const QTensor* ts, const int* 
 // to_float of a whole descriptor list in ONE launch: the tile chunks (strided views, tensors that are not
 // float4-addressable -- few, latency-bound workgroups) come first in the grid and finish under the stream of flat
 // chunks; as a launch of their own they ran 20-50 us BEHIND the big kernel on the same stream.
-__global__ __launch_bounds__(256) void quant_decode_all_kernel(const QTensor* ts, const int* cmap, int fch, int tch) {
+__global__ __launch_bounds__(256) void quant_decode_all_kernel(const QTensor* ts, const int* fmap, const int* tmap,
+                                                               int tch) {
   if ((int)blockIdx.x < tch) {
-    quant_decode_tile(ts, cmap + fch, (int)blockIdx.x);
+    quant_decode_tile(ts, tmap, (int)blockIdx.x);
     return;
   }
   const int chunk = (int)blockIdx.x - tch;
-  const QTensor* t = &ts[cmap[chunk]];
-  const int local = chunk - t->fchunk0;
-  const bool full = (long long)(local + 1) * QFLAT <= t->rows * t->cols;
-  if (t->bits == 16) {
-    if (full) quant_flat_chunk<2, true, 16>(t, local, nullptr);
-    else quant_flat_chunk<2, false, 16>(t, local, nullptr);
-  } else {
-    if (full) quant_flat_chunk<2, true, 8>(t, local, nullptr);
-    else quant_flat_chunk<2, false, 8>(t, local, nullptr);
-  }
+  const QTensor* t = &ts[fmap[chunk]];
+  quant_flat_dispatch<2>(t, chunk - t->chunk0, t->cols, nullptr);
 }
-
-static bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
-// Validates descriptors and fills the device table image.  Returns total chunks or <0.
-static long long build_tensors(const ps_quant_desc* desc, int count, bool encode,
-                               std::vector<QTensor>& ht, size_t& total_cols) {
-  ht.resize(count);
-  const bool flat_on = psh::resolve(nullptr).quant_flat != 0;
-  const bool strip_on = psh::resolve(nullptr).quant_strip != 0;
-  long long chunk0 = 0;
-  total_cols = 0;
-  for (int i = 0; i < count; ++i) {
-    const ps_quant_desc& d = desc[i];
-    if (d.rows < 0 || d.cols < 0 || (d.bits != 8 && d.bits != 16)) return PS_EINVAL;
-    if (d.rows > 0 && d.cols > 0) {
-      if (!d.fvalue || !d.codes || !d.bucket_size || d.ld < d.cols || d.ldq < d.cols)
-        return PS_EINVAL;
-      if (d.extract_diagonal && (!d.diagonal || d.rows != d.cols)) return PS_EINVAL;  // QU:67-69
-    }
-    QTensor& t = ht[i];
-    t.fin = d.fvalue; t.fout = d.fvalue; t.codes = d.codes; t.diag = d.diagonal;
-    t.bucket = d.bucket_size; t.colmax = nullptr;
-    t.rows = d.rows; t.cols = d.cols; t.ld = d.ld; t.ldq = d.ldq;
-    t.bits = d.bits; t.extract = d.extract_diagonal ? 1 : 0;
-    const size_t code_vec = d.bits == 16 ? 8 : 4;
-    t.vec4 = (d.cols % 4 == 0 && d.ld % 4 == 0 && d.ldq % 4 == 0 && aligned(d.fvalue, 16) &&
-              aligned(d.codes, code_vec) && aligned(d.bucket_size, 16)) ? 1 : 0;
-    t.flat = (flat_on && t.vec4 && d.ld == d.cols && d.ldq == d.cols && d.cols <= QFLAT_MAXC && d.rows > 0 &&
-              d.cols > 0 && count <= QMAXT && aligned(d.codes, 16)) ? 1 : 0;
-    // quantize: matrices of 64 ... 1024 rows are encoded from registers in one read (quant_strip_kernel),
-    // (taller ones, up to 4096 rows, in parts of 1024 rows that merge their column maxima: QTensor::team)
-    t.strip = (encode && strip_on && t.flat && d.rows >= QS_MINR && d.rows <= 4LL * QS_NV * QS_GROUPS &&
-               (d.rows * d.cols) * 4 < (1LL << 31)) ? 1 : 0;
-    t.team = t.strip ? (int)((d.rows + QS_NV * QS_GROUPS - 1) / (QS_NV * QS_GROUPS)) : 1;
-    t.sarrive = nullptr;
-    t.schunks = t.strip ? (int)((d.cols + QS_COLS - 1) / QS_COLS) * t.team : 0;
-    // ... and small ones of any layout by one workgroup of the same launch (quant_small_body)
-    // (short ones, rows < 64, of any width; others -- odd sizes, strided views -- up to 1024 rows)
-    t.small = (encode && strip_on && !t.strip && d.rows > 0 && d.cols > 0 && d.rows <= QS_NV * QS_GROUPS) ? 1 : 0;
-    t.small_w = t.small ? (int)std::min<long long>(std::min<long long>(d.cols, QSM_COLS), QSM_ELEMS / d.rows) : 0;
-    if (t.strip || t.small) t.flat = 0;
-    t.fchunks = t.flat ? (int)((d.rows * d.cols + QFLAT - 1) / QFLAT) : 0;
-    t.strips = (int)((d.cols + QW - 1) / QW);
-    const long long rcs = (d.rows + QR - 1) / QR;
-    t.chunk0 = (int)chunk0;
-    chunk0 += (d.rows > 0 && d.cols > 0) ? t.strips * rcs : 0;
-    if (chunk0 > 0x7fffffffLL) return PS_EUNSUPPORTED;
-    total_cols += psh::align_up((size_t)d.cols, 4);
-  }
-  return chunk0;
-}
-
-// Per-chunk tensor index: first the flat chunks (contiguous float4-addressable tensors), then the
-// 64 x 256 tile chunks of the other tensors; chunk0 / fchunk0 of every tensor are set to its first
-// chunk inside its own list.
-static void build_chunk_maps(std::vector<QTensor>& ht, std::vector<int>& map, long long& fch,
-                             long long& tch, long long* sch_out = nullptr, long long* nsm_out = nullptr) {
-  fch = 0; tch = 0;
-  for (size_t i = 0; i < ht.size(); ++i) {
-    QTensor& t = ht[i];
-    if (t.flat) { t.fchunk0 = (int)fch; fch += t.fchunks; }
-  }
-  map.reserve((size_t)fch);
-  for (size_t i = 0; i < ht.size(); ++i)
-    if (ht[i].flat) map.insert(map.end(), (size_t)ht[i].fchunks, (int)i);
-  for (size_t i = 0; i < ht.size(); ++i) {
-    QTensor& t = ht[i];
-    if (t.flat || t.strip || t.small || t.rows <= 0 || t.cols <= 0) continue;
-    const long long n = (long long)t.strips * ((t.rows + QR - 1) / QR);
-    t.chunk0 = (int)tch;
-    tch += n;
-    map.insert(map.end(), (size_t)n, (int)i);
-  }
-  long long sch = 0;   // the register-resident strips (quantize only) come last in the table
-  for (size_t i = 0; i < ht.size(); ++i) {
-    QTensor& t = ht[i];
-    if (!t.strip) continue;
-    t.schunk0 = (int)sch;
-    sch += t.schunks;
-    map.insert(map.end(), (size_t)t.schunks, (int)i);
-  }
-  if (sch_out) *sch_out = sch;
-  // the small tensors (quantize only): tensor indices, last in the table
-  long long nsm = 0;
-  for (size_t i = 0; i < ht.size(); ++i) {
-    if (!ht[i].small) continue;
-    for (long long c0 = 0; c0 < ht[i].cols; c0 += ht[i].small_w) {   // (tensor, first column) pairs
-      map.push_back((int)i); map.push_back((int)c0); ++nsm;
-    }
-  }
-  if (nsm_out) *nsm_out = nsm;
-}
-
-// Tensors without chunks would break the chunk -> tensor search (equal chunk0 keys resolve to
-// the LAST tensor with that key, which is the one that owns the chunk, because empty tensors
-// add no chunks); nothing else to do for them.
 
 }  // namespace psk
 
 using namespace psk;
 
-// upper bound of the per-chunk table (a tensor is in one of the two chunk lists)
-static size_t quant_map_bytes(const ps_quant_desc* desc, int count) {
-  size_t n = 0;
-  for (int i = 0; i < count; ++i) {
-    if (desc[i].rows <= 0 || desc[i].cols <= 0) continue;
-    const size_t flat = (size_t)((desc[i].rows * desc[i].cols + QFLAT - 1) / QFLAT);
-    const size_t tile = (size_t)((desc[i].cols + QW - 1) / QW) * (size_t)((desc[i].rows + QR - 1) / QR);
-    const size_t strips = 4 * (size_t)((desc[i].cols + QS_COLS - 1) / QS_COLS);
-    // (small tensors: one pair of words per range of >= 64 columns, or one pair in all)
-    n += std::max(std::max(flat, tile), strips) + 2 * ((size_t)desc[i].cols / 64 + 1);
-  }
-  return psh::align_up(sizeof(int) * (n + 1), 256);
+static int quant_cus() {
+  static const int cus = [] {
+    int dev = 0, n = 0;
+    const bool ok = hipGetDevice(&dev) == hipSuccess &&
+                    hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0;
+    return ok ? n : 256;
+  }();
+  return cus;
 }
 
-static int quant_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess &&
-        prop.multiProcessorCount > 0)
-      cus = prop.multiProcessorCount;
-  }
-  return cus;
+// bytes of the two tables in the workspace (bounds: the queries build no plan)
+static size_t quant_tables_bytes(const ps_quant_desc* desc, int count) {
+  return psh::align_up(sizeof(QTensor) * count, 256) +
+         psh::align_up(sizeof(int) * (quant_table_bound(desc, count) + 1), 256);
+}
+
+// tensor table and per-chunk table of a plan into the arena and on their way to the device
+static int quant_upload_plan(hipStream_t st, psh::Arena& ar, const QuantPlan& p, const QTensor*& dt, const int*& dmap) {
+  QTensor* t = ar.take<QTensor>(p.tensors.size());
+  int* m = ar.take<int>(p.table.size() + 1);
+  if (ar.overflow) return PS_EWORKSPACE;
+  PS_RC(psh::upload_async(st, t, p.tensors.data(), sizeof(QTensor) * p.tensors.size()));
+  PS_RC(psh::upload_async(st, m, p.table.data(), sizeof(int) * p.table.size()));
+  dt = t; dmap = m;
+  return PS_OK;
 }
 
 extern "C" size_t ps_quantize_workspace_bytes(const ps_quant_desc* desc, int count) {
   if (!desc || count <= 0) return 0;
-  size_t cols = 0;
-  // per tensor: column maxima + one arrival counter per strip of 64 columns (tall strips); + the strip queue's counter
-  for (int i = 0; i < count; ++i) {
-    const size_t c = (size_t)(desc[i].cols > 0 ? desc[i].cols : 0);
-    cols += psh::align_up(c, 4) + (c + QS_COLS - 1) / QS_COLS;
-  }
-  return psh::align_up(sizeof(QTensor) * count, 256) + psh::align_up(sizeof(unsigned) * (cols + 4), 256) +
-         quant_map_bytes(desc, count) + 1024;
+  return quant_tables_bytes(desc, count) + psh::align_up(sizeof(unsigned) * quant_scratch_bound(desc, count), 256) +
+         1024;
 }
 
 extern "C" int ps_quantize_f32(void* stream, const ps_quant_desc* desc, int count, void* workspace,
@@ -1021,55 +844,33 @@ extern "C" int ps_quantize_f32(void* stream, const ps_quant_desc* desc, int coun
   PS_DEVICE_CHECK();
   if (!desc || count <= 0 || !workspace) return PS_EINVAL;
   if (workspace_bytes < ps_quantize_workspace_bytes(desc, count)) return PS_EWORKSPACE;
-  std::vector<QTensor> ht;
-  size_t total_cols = 0;
-  const long long chunks = build_tensors(desc, count, true, ht, total_cols);
-  if (chunks < 0) return (int)chunks;
-  if (chunks == 0) return PS_OK;
+  QuantPlan p;
+  PS_RC(quant_build_plan(desc, count, true, p));
+  if (p.table.empty()) return PS_OK;
   hipStream_t st = (hipStream_t)stream;
   psh::Arena ar(workspace, workspace_bytes);
-  QTensor* dt = ar.take<QTensor>(count);
-  size_t team_strips = 0;
-  for (int i = 0; i < count; ++i)
-    if (ht[i].team > 1) team_strips += (size_t)ht[i].schunks / (size_t)ht[i].team;
-  // column maxima | the strip queue's counter (4 words) | arrival counters of the tall strips: one memset
-  unsigned* colmax = ar.take<unsigned>(total_cols + 4 + team_strips);
+  unsigned* scratch = ar.take<unsigned>(p.scratch_words());
   if (ar.overflow) return PS_EWORKSPACE;
-  size_t off = 0, soff = 0;
-  for (int i = 0; i < count; ++i) {
-    ht[i].colmax = colmax + off;
-    off += psh::align_up((size_t)ht[i].cols, 4);
-    if (ht[i].team > 1) {
-      ht[i].sarrive = colmax + total_cols + 4 + soff;
-      soff += (size_t)ht[i].schunks / (size_t)ht[i].team;
-    }
-  }
-  PS_HIP(hipMemsetAsync(colmax, 0, sizeof(unsigned) * (total_cols + 4 + team_strips), st));
-  // flat tensors: one launch per pass over chunks of consecutive elements; the others (odd sizes,
-  // strided views) keep the tile kernels
-  std::vector<int> hmap;
-  long long fch = 0, tch = 0, sch = 0, nsm = 0;
-  build_chunk_maps(ht, hmap, fch, tch, &sch, &nsm);
-  int* dmap = ar.take<int>(hmap.size() + 1);
-  if (ar.overflow) return PS_EWORKSPACE;
-  PS_RC(psh::upload_async(st, dt, ht.data(), sizeof(QTensor) * count));
-  PS_RC(psh::upload_async(st, dmap, hmap.data(), sizeof(int) * hmap.size()));
+  p.bind_scratch(scratch);
+  PS_HIP(hipMemsetAsync(scratch, 0, sizeof(unsigned) * p.scratch_words(), st));
+  const QTensor* dt = nullptr;
+  const int* dmap = nullptr;
+  PS_RC(quant_upload_plan(st, ar, p, dt, dmap));
   const dim3 blk(256);
-  if (sch + nsm > 0) {
-    // the small tensors' workgroups, then the persistent ones: one per CU, the strips beyond the first 256 from a
-    // queue (the counter behind the column maxima)
-    const long long grid = nsm + std::min<long long>(sch, quant_cus());
+  if (p.strip_items + p.small_items > 0) {
+    // the small tensors' workgroups, then the persistent ones: one per CU, the strips beyond the first from a queue
+    const long long grid = (long long)p.small_items + std::min(p.strip_items, quant_cus());
     if (grid > 0x7fffffffLL) return PS_EUNSUPPORTED;
-    hipLaunchKernelGGL(quant_strip_kernel, dim3((unsigned)grid), dim3(QS_THREADS), 0, st, dt, dmap + fch + tch,
-                       (int)sch, colmax + total_cols, dmap + fch + tch + sch, (int)nsm);
+    hipLaunchKernelGGL(quant_strip_kernel, dim3((unsigned)grid), dim3(QS_THREADS), 0, st, dt, dmap + p.strip_off,
+                       p.strip_items, scratch + p.queue_off(), dmap + p.small_off, p.small_items);
   }
-  if (fch > 0) {
-    hipLaunchKernelGGL(quant_flat_kernel<0>, dim3((unsigned)fch), blk, 0, st, dt, dmap);
-    hipLaunchKernelGGL(quant_flat_kernel<1>, dim3((unsigned)fch), blk, 0, st, dt, dmap);
+  if (p.flat_chunks > 0) {
+    hipLaunchKernelGGL(quant_flat_kernel<0>, dim3((unsigned)p.flat_chunks), blk, 0, st, dt, dmap + p.flat_off);
+    hipLaunchKernelGGL(quant_flat_kernel<1>, dim3((unsigned)p.flat_chunks), blk, 0, st, dt, dmap + p.flat_off);
   }
-  if (tch > 0) {
-    hipLaunchKernelGGL(quant_colmax_kernel, dim3((unsigned)tch), blk, 0, st, dt, dmap + fch, 0);
-    hipLaunchKernelGGL(quant_encode_kernel, dim3((unsigned)tch), blk, 0, st, dt, dmap + fch, 0);
+  if (p.tile_chunks > 0) {
+    hipLaunchKernelGGL(quant_colmax_kernel, dim3((unsigned)p.tile_chunks), blk, 0, st, dt, dmap + p.tile_off);
+    hipLaunchKernelGGL(quant_encode_kernel, dim3((unsigned)p.tile_chunks), blk, 0, st, dt, dmap + p.tile_off);
   }
   PS_LAUNCH_CHECK();
   return PS_OK;
@@ -1077,7 +878,7 @@ extern "C" int ps_quantize_f32(void* stream, const ps_quant_desc* desc, int coun
 
 extern "C" size_t ps_dequantize_workspace_bytes(const ps_quant_desc* desc, int count) {
   if (!desc || count <= 0) return 0;
-  return psh::align_up(sizeof(QTensor) * count, 256) + quant_map_bytes(desc, count) + 1024;
+  return quant_tables_bytes(desc, count) + 1024;
 }
 
 extern "C" int ps_dequantize_f32(void* stream, const ps_quant_desc* desc, int count, void* workspace,
@@ -1085,25 +886,19 @@ extern "C" int ps_dequantize_f32(void* stream, const ps_quant_desc* desc, int co
   PS_DEVICE_CHECK();
   if (!desc || count <= 0 || !workspace) return PS_EINVAL;
   if (workspace_bytes < ps_dequantize_workspace_bytes(desc, count)) return PS_EWORKSPACE;
-  std::vector<QTensor> ht;
-  size_t total_cols = 0;
-  const long long chunks = build_tensors(desc, count, false, ht, total_cols);
-  if (chunks < 0) return (int)chunks;
-  if (chunks == 0) return PS_OK;
+  QuantPlan p;
+  PS_RC(quant_build_plan(desc, count, false, p));
+  if (p.table.empty()) return PS_OK;
   hipStream_t st = (hipStream_t)stream;
   psh::Arena ar(workspace, workspace_bytes);
-  QTensor* dt = ar.take<QTensor>(count);
-  if (ar.overflow) return PS_EWORKSPACE;
-  std::vector<int> hmap;
-  long long fch = 0, tch = 0;
-  build_chunk_maps(ht, hmap, fch, tch);
-  int* dmap = ar.take<int>(hmap.size() + 1);
-  if (ar.overflow) return PS_EWORKSPACE;
-  PS_RC(psh::upload_async(st, dt, ht.data(), sizeof(QTensor) * count));
-  PS_RC(psh::upload_async(st, dmap, hmap.data(), sizeof(int) * hmap.size()));
-  if (fch + tch > 0x7fffffffLL) return PS_EUNSUPPORTED;
-  hipLaunchKernelGGL(quant_decode_all_kernel, dim3((unsigned)(fch + tch)), dim3(256), 0, st, dt, dmap, (int)fch,
-                     (int)tch);
+  const QTensor* dt = nullptr;
+  const int* dmap = nullptr;
+  PS_RC(quant_upload_plan(st, ar, p, dt, dmap));
+  // the tile chunks first in the grid (see quant_decode_all_kernel)
+  const long long grid = (long long)p.flat_chunks + p.tile_chunks;
+  if (grid > 0x7fffffffLL) return PS_EUNSUPPORTED;
+  hipLaunchKernelGGL(quant_decode_all_kernel, dim3((unsigned)grid), dim3(256), 0, st, dt, dmap + p.flat_off,
+                     dmap + p.tile_off, p.tile_chunks);
   PS_LAUNCH_CHECK();
   return PS_OK;
 }

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../include/ps_api.h"
+#include "../precondition_amd/csrc/quant_plan.h"
 
 #define CHECK(cond)                                                       \
   do {                                                                    \
@@ -96,8 +97,20 @@ int main() {
     qd[i].rows = n[i]; qd[i].cols = n[i]; qd[i].ld = n[i]; qd[i].ldq = n[i];
     qd[i].bits = (i & 1) ? 8 : 16; qd[i].extract_diagonal = 1;
   }
-  (void)ps_quantize_workspace_bytes(qd.data(), (int)qd.size());
-  (void)ps_dequantize_workspace_bytes(qd.data(), (int)qd.size());
+  // the plans the two calls would build: their tables fit what the workspace queries reserve
+  for (int encode = 0; encode < 2; ++encode) {
+    psk::QuantPlan plan;
+    CHECK(psk::quant_build_plan(qd.data(), (int)qd.size(), encode != 0, plan) == PS_OK);
+    CHECK(plan.tensors.size() == qd.size());
+    CHECK(plan.table.size() == (size_t)plan.flat_chunks + plan.tile_chunks + plan.strip_items + 2 * (size_t)plan.small_items);
+    CHECK(plan.table.size() <= psk::quant_table_bound(qd.data(), (int)qd.size()));
+    CHECK(plan.scratch_words() <= psk::quant_scratch_bound(qd.data(), (int)qd.size()));
+    for (int owner : plan.table) CHECK(owner >= 0);
+    const size_t ws = encode ? ps_quantize_workspace_bytes(qd.data(), (int)qd.size())
+                             : ps_dequantize_workspace_bytes(qd.data(), (int)qd.size());
+    CHECK(ws > sizeof(psk::QTensor) * qd.size() + sizeof(int) * plan.table.size() +
+                   (encode ? sizeof(unsigned) * plan.scratch_words() : 0));
+  }
   CHECK(ps_mat_power_workspace_bytes(512, 6) > 0);
 
   // rejection paths of the compute entry points (no device here: PS_EDEVICE / a HIP error, or

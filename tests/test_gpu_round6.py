@@ -247,28 +247,8 @@ def test_quantize_register_strips_on_rounding_boundaries_and_extreme_scales(shap
   wide and short ones ([1, 197, 768] embeddings: ranges of columns, one workgroup each).  Codes, diagonal and bucket sizes
   bit-identical to the oracle's (numpy float32 division is correctly rounded; np.round is half-even)."""
   from oracle import quantization_oracle as qorc
-  rng = np.random.default_rng(hash((shape, bits, 6)) % (2 ** 31))
-  rows, cols = shape
-  nb = np.float32(127.0 if bits == 8 else 32767.0)
-  colmax = (rng.uniform(1.0, 2.0, size=cols) * np.exp2(rng.integers(-6, 7, size=cols))).astype(np.float32)
-  wild = rng.uniform(size=cols) < 0.15
-  colmax[wild] = (colmax[wild] * np.exp2(rng.choice([-80.0, -61.0, -59.0, 59.0, 61.0, 80.0], size=int(wild.sum())))
-                  ).astype(np.float32)
-  bucket = (colmax / nb).astype(np.float32)
-  k = rng.integers(-int(nb) + 1, int(nb) - 1, size=shape).astype(np.float64)
-  x = ((k + 0.5) * bucket.astype(np.float64)[None, :]).astype(np.float32)       # on a rounding boundary (or next to it)
-  bump = rng.integers(-1, 2, size=shape)
-  x = np.where(bump > 0, np.nextafter(x, np.float32(np.inf)), np.where(bump < 0, np.nextafter(x, np.float32(-np.inf)), x))
-  x = x.astype(np.float32)
-  x[rng.uniform(size=shape) < 0.05] = 0.0
-  x[rng.uniform(size=shape) < 0.02] = np.float32(1e-41)                            # denormal
-  x[rng.integers(0, rows, size=cols), np.arange(cols)] = colmax                     # the column maximum itself
-  if cols > 2:
-    x[:, 1] = 0.0
-  if extract:
-    x = np.triu(x) + np.triu(x, 1).T
-    x[np.arange(rows), np.arange(rows)] = (colmax * 7).astype(np.float32)           # diagonal above every column maximum
-  x = np.ascontiguousarray(x, np.float32)
+  from tests.quant_inputs import rounding_boundary_input
+  x = rounding_boundary_input(shape, bits, extract)
   npdt = np.int8 if bits == 8 else np.int16
   oq, od, ob = qorc.quantize(x, npdt, extract)
   q, d, b = K().quantize_grouped([torch.tensor(x, device=device)], _TQ6[bits], extract)[0]

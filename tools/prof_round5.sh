@@ -17,7 +17,7 @@ bash tools/prof_cfg2.sh r05_headline --workload headline_64x1024_p4 > $R/prof_he
 python3 tools/summarize_pmc2.py gpurun_out/r05_headline $R/r05_headline_pmc_by_kernel.json > /dev/null 2>&1
 cp gpurun_out/r05_headline/trace/*/*kernel_stats.csv $R/r05_headline_kernel_stats.csv 2>/dev/null
 cp gpurun_out/r05_headline/bench_trace.json $R/r05_headline_bench_under_rocprof.json 2>/dev/null
-for pair in "eigh:tools/dev_eigh_one.py" "update_step_vitb_donated:tools/dev_update_step.py --donate" "update_step_vitb:tools/dev_update_step.py" "quant:tools/dev_r5_quant.py 1" "vitb:tools/dev_vitb_step.py" "fd_cfg5:tools/dev_fd_profile.py"; do
+for pair in "eigh:tools/dev_eigh_one.py" "update_step_vitb_donated:tools/dev_update_step.py --donate" "update_step_vitb:tools/dev_update_step.py" "vitb:tools/dev_vitb_step.py" "fd_cfg5:tools/dev_fd_profile.py"; do
   name=${pair%%:*}; cmd=${pair#*:}
   bash tools/prof_pmc.sh r05_$name $cmd > $R/prof_$name.log 2>&1
   cp gpurun_out/r05_$name/summary.json $R/r05_${name}_pmc_by_kernel.json 2>/dev/null
